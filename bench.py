@@ -7,7 +7,7 @@ is already resident in HBM: forward of obs and next_obs through the conv auto-en
 BASELINE.json configs[1]: synthetic 224x224x3 observations, --losses autoencoder, custom_cnn, state-dim 200, bs=256.
 `--losses vae` / `--losses autoencoder inverse forward` select configs[2] / configs[3]'s per-GPU workload.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 N > 1 runs one process per GPU over RCCL.  Either a launcher provides the ranks (python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* are read from the environment), or — when
@@ -20,10 +20,13 @@ kernel (conv64_fwd_kernel), in a short instrumented pass of the same steps RIGHT
 inside the timed region cost ~0.5 % of the headline, VERDICT r2 item 11 — the timed region carries no instrumentation);
 "cpu_baseline" times the CPU oracle (plain torch fp32 twin
 of the reference path) on the host cores for a bounded sample — a reported baseline, not a target.
+`--dump-outputs DIR` writes what the last timed step computed (step_outputs) as DIR/<name>.npy, so that two builds run with the same
+arguments — identical seeded inputs — can be compared output for output.
 """
 import argparse
 import json
 import os
+import re
 import sys
 import time
 
@@ -37,6 +40,8 @@ import torch  # noqa: E402
 
 PEAK_FP32_MFMA_TFLOPS = 157.3  # MI355X dense fp32 matrix peak (MI355X_MICROARCH.md)
 PEAK_HBM_GBS = 8000.0
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_MAX_ELEMENTS = 2 << 20  # ... and per array: a larger one is written as a fixed, seeded sample of this many elements (<name>_sample)
 
 
 def synthetic_batch(B, C, seed, device):
@@ -47,6 +52,40 @@ def synthetic_batch(B, C, seed, device):
     # the two frames are the halves of ONE device buffer, as the learner's feed delivers them (SRL4robotics._toDevicePair)
     both = torch.from_numpy(np.concatenate((obs, next_obs), 0)).to(device)
     return both[:B], both[B:], torch.from_numpy(actions).view(-1, 1).to(device)
+
+
+def step_outputs(srl, loss_manager, loss):
+    """What a caller of SRL4robotics.trainStep holds after one step, as float32 host arrays: the total loss it returned, the individual
+    losses in the LossManager, the parameters the Adam step has just updated, the gradient bucket that step consumed and the BatchNorm
+    running statistics.  Called right after a timed region (the clock has stopped; the instrumented steps behind it move the
+    parameters again)."""
+    out = {"loss": loss.detach().float().reshape(1)}
+    for name, value in zip(loss_manager.names, loss_manager.losses):
+        out["loss_" + re.sub(r"\W+", "_", name)] = value.detach().float().reshape(1)
+    out["params"] = srl.flat_params.flat.detach()
+    out["grad"] = srl.flat_params.grad.detach()
+    stats = [b.detach().float().reshape(-1) for b in srl.model.buffers() if b.is_floating_point()]
+    if stats:
+        out["bn_running_stats"] = torch.cat(stats)
+    arrays = {}
+    for name, t in out.items():
+        a = t.cpu().numpy().astype(np.float32, copy=False)
+        if a.size > DUMP_MAX_ELEMENTS:  # (same size -> same indices in every run)
+            idx = np.sort(np.random.RandomState(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))
+            name, a = name + "_sample", a[idx]
+        arrays[name] = a
+    return arrays
+
+
+def dump_outputs(directory, arrays):
+    """arrays -> directory/<name>.npy; returns the names written."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %.1f MB (> %d MB)" % (total / 1e6, DUMP_MAX_BYTES >> 20))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in sorted(arrays.items()):
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def host_cores():
@@ -240,7 +279,7 @@ def self_launch(n, argv, script=None):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (exactly this many)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch-size", type=int, default=256, help="per-GPU minibatch (samples; 2 frames each)")
     ap.add_argument("--losses", nargs="+", default=["autoencoder"])
@@ -267,10 +306,15 @@ def main():
     ap.add_argument("--no-strong-leg", action="store_true",
                     help="with --gpus N > 1: skip the strong-scaling leg (global batch = --batch-size, i.e. bs / N per GPU) reported as `strong`")
     ap.add_argument("--allow-short", action="store_true",
-                    help="print the line even when the timed region is shorter than 0.1 s (functional tests on tiny batches)")
+                    help="no warning on stderr when the timed region is shorter than 0.1 s (functional tests on tiny batches)")
     ap.add_argument("--host-input-nhwc", action="store_true",
                     help="with --host-input: frames as decoded ([B,H,W,C]) + the separate srlz_normalize_u8 pass (A/B)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (loss, individual losses, updated parameters, gradient bucket, BatchNorm "
+                         "running statistics; the VAE leg's with the prefix vae_) as DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -372,7 +416,7 @@ def main():
 
     def timed(step_fn, warmup, steps):
         """`warmup` untimed steps, then EXACTLY `steps` steps bracketed by barrier + synchronize.  Returns (seconds: max over the
-        ranks, seconds on this rank's own clock, the steps' total losses)."""
+        ranks, seconds on this rank's own clock, the steps' total losses as the 0-dim device tensors the steps returned)."""
         for _ in range(warmup):
             step_fn()
         sync()
@@ -387,17 +431,16 @@ def main():
                 t = t.to(device)
             torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
             worst = float(t.item())
-        return worst, own, torch.stack(totals).tolist()
+        return worst, own, totals
 
     dt, own_dt, last_losses = timed(step, args.warmup, args.steps)
-    if dt < 0.1 and not args.allow_short:  # (0.2 s until round 6: twenty steps of the bs = 256 step are 0.23 s by now)
-        # (dt is the maximum over the ranks, the same number everywhere: every rank takes this exit, here, before the other legs — a
-        # rank 0 leaving alone would strand the others in their next collective until the RCCL timeout)
-        if world > 1:
-            torch.distributed.destroy_process_group()
-        msg = "bench.py: the timed region was %.3f s (< 0.1 s: %d steps of %.3f ms) — too short to be a measurement; " \
-              "raise --steps (or pass --allow-short for a functional check)" % (dt, args.steps, 1e3 * dt / args.steps)
-        raise SystemExit(msg if rank == 0 else 1)
+    dumped = {}
+    if args.dump_outputs and rank == 0:
+        dumped.update(step_outputs(srl, loss_manager, last_losses[-1]))
+    if dt < 0.1 and not args.allow_short and rank == 0:
+        # (the line is still printed: --steps sets the number of timed steps, and a caller sizes its next run by ms_per_step)
+        print("bench.py: the timed region was %.3f s (< 0.1 s: %d steps of %.3f ms) — too short to be a measurement; raise --steps "
+              "(or pass --allow-short for a functional check)" % (dt, args.steps, 1e3 * dt / args.steps), file=sys.stderr)
     rank_ms = None
     if world > 1:  # every rank's own clock around the same K steps: skew between the ranks shows here
         rank_ms = [None] * world
@@ -448,10 +491,12 @@ def main():
             sys.stdout = stdout
         lm_vae = LossManager(srl_vae.model, None)
         v_dt, _, v_losses = timed(lambda: srl_vae.trainStep(obs, next_obs, actions, lm_vae), args.warmup, args.steps)
+        if args.dump_outputs and rank == 0:
+            dumped.update(("vae_" + k, a) for k, a in step_outputs(srl_vae, lm_vae, v_losses[-1]).items())
         v_tf = 2320.0e6 * 2 * B / (v_dt / args.steps) / 1e12
         vae = {"workload": "synthetic 224x224x3 obs, --losses vae (beta=1), custom_cnn, state-dim %d, bs=%d per GPU" % (args.state_dim, B),
                "ms_per_step": round(1e3 * v_dt / args.steps, 3), "images_per_s": round(2 * B * world * args.steps / v_dt, 1),
-               "steps": args.steps, "warmup": args.warmup, "timed_region_s": round(v_dt, 4), "final_loss": round(v_losses[-1], 6),
+               "steps": args.steps, "warmup": args.warmup, "timed_region_s": round(v_dt, 4), "final_loss": round(float(v_losses[-1]), 6),
                "step_roofline": {"algorithmic_tflop_per_step": round(2320.0e6 * 2 * B / 1e12, 4), "achieved_tflops": round(v_tf, 2),
                                  "frac_of_fp32_mfma_peak": round(v_tf / PEAK_FP32_MFMA_TFLOPS, 4)}}
         del srl_vae, lm_vae
@@ -505,7 +550,7 @@ def main():
                        # (from the process group and its gathered device table, not from the environment)
                        "rccl_ranks": placement["ranks"] if world > 1 else 1,
                        "devices": placement["devices"] if world > 1 else 1,
-                       "final_loss": round(last_losses[-1], 6)},
+                       "final_loss": round(float(last_losses[-1]), 6)},
         }
         if vae is not None:
             out["vae"] = vae
@@ -626,6 +671,8 @@ def main():
                                  "aggregate_executed_frac": frac_ex.get("all"), "executed_frac_conv2": frac_ex.get("conv2"),
                                  "aggregate_tflops": round(frac.get("all", 0.0) * PEAK_FP32_MFMA_TFLOPS, 2), "images_per_launch": 2 * B,
                                  "timing": "same instrumented pass as roofline (HIP events on the launch stream)"}
+        if args.dump_outputs:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, dumped)}
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(list(args.losses), full=args.cpu_baseline_full)
         print(json.dumps(out))

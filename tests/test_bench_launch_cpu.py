@@ -63,3 +63,41 @@ def test_gpus_must_match_the_launcher(tmp_path):
     proc = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2"], env=env, stdout=subprocess.PIPE,
                           stderr=subprocess.PIPE, timeout=120)
     assert proc.returncode != 0 and b"launcher started 1 rank" in proc.stderr
+
+
+def test_steps_must_be_positive():
+    proc = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "0"], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                          timeout=120)
+    assert proc.returncode == 2 and b"--steps must be >= 1" in proc.stderr
+
+
+def test_step_outputs_and_dump(tmp_path):
+    """--dump-outputs: what a caller of trainStep holds after the step, as float32 arrays; an array above the per-array limit becomes
+    the same seeded sample in every run; the files stay within the size budget."""
+    import types
+    import numpy as np
+    import torch
+    model = torch.nn.Sequential(torch.nn.Conv2d(3, 4, 3), torch.nn.BatchNorm2d(4))
+    n = bench.DUMP_MAX_ELEMENTS + 5
+    flat = types.SimpleNamespace(flat=torch.arange(n, dtype=torch.float32), grad=torch.full((16,), 0.5))
+    srl = types.SimpleNamespace(flat_params=flat, model=model)
+    lm = types.SimpleNamespace(names=["reconstruction_loss"], losses=[torch.tensor(0.25)])
+    a = bench.step_outputs(srl, lm, torch.tensor(1.5))
+    assert sorted(a) == ["bn_running_stats", "grad", "loss", "loss_reconstruction_loss", "params_sample"]
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["loss"].tolist() == [1.5] and a["loss_reconstruction_loss"].tolist() == [0.25] and a["grad"].tolist() == [0.5] * 16
+    assert a["bn_running_stats"].tolist() == [0.0] * 4 + [1.0] * 4  # running_mean, running_var (num_batches_tracked is no float)
+    s = a["params_sample"]
+    assert s.size == bench.DUMP_MAX_ELEMENTS and np.all(np.diff(s) > 0) and s[-1] < n
+    assert np.array_equal(bench.step_outputs(srl, lm, torch.tensor(1.5))["params_sample"], s)
+    names = bench.dump_outputs(str(tmp_path / "out"), a)
+    assert names == sorted(a)
+    for k in names:
+        assert np.array_equal(np.load(str(tmp_path / "out" / (k + ".npy"))), a[k])
+    big = {"x": np.zeros(bench.DUMP_MAX_BYTES // 4 + 1, np.float32)}
+    try:
+        bench.dump_outputs(str(tmp_path / "big"), big)
+        raise AssertionError("over the budget")
+    except SystemExit as e:
+        assert "--dump-outputs would write" in str(e)
+    assert not os.path.exists(str(tmp_path / "big"))
