@@ -399,6 +399,50 @@ int srlz_nchw_to_nhwc(const float* src, float* dst, int n, int c, int h, int w, 
 int srlz_nhwc_to_nchw(const float* src, float* dst, int n, int c, int h, int w, srlz_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Dense layers of the mlp / linear models (csrc/dense.hip): the nn.Linear whose input or output is the flattened image,
+ * K = input_dim = C * W * H (preprocess.py getInputDim), M = images of the call, n = the small side (1..256).
+ * x / target come as fp32 [M][K] or as the loader's planar uint8 frames [M][C][W][H] with the srlz_normalize_lut table
+ * (plane = W * H; the two routes agree bit for bit).  W in torch [out, in] layout.  No float atomics: deterministic.
+ * ------------------------------------------------------------------------------------------------------------ */
+/* 1 when M, n, K, plane fit the kernels (n <= 256, K = 3 or 6 planes, every offset below 2^31), else 0 with the reason in
+ * srlz_last_error().  Every dense launcher checks it. */
+int srlz_dense_supported(int M, int n, int K, int plane);
+/* y[M,n] = act(x . W[n,K]^T + b), act 0 none / 1 ReLU / 2 tanh — nn.Linear(input_dim, h) of autoencoders.py:15,51,
+ * vae.py:17 (+ ReLU, vae.py:35), priors.py:89 (+ ReLU), priors.py:116.  x or x_u8 (+ lut) is non-NULL.  Split over K,
+ * partials in ws (srlz_dense_in_workspace bytes) summed in a fixed order. */
+size_t srlz_dense_in_workspace(int M, int n, int K);
+int srlz_dense_in_fwd(const float* x, const uint8_t* x_u8, const float* norm_lut, const float* w, const float* b, float* y, int M,
+                      int n, int K, int plane, int act, void* ws, size_t ws_bytes, srlz_stream_t stream);
+/* dW[n,K] = dy^T . x, db[n] = sum_m dy (db may be NULL) — the weight gradient of the layers above (no data gradient: the
+ * images need none). */
+int srlz_dense_in_wgrad(const float* dy, const float* x, const uint8_t* x_u8, const float* norm_lut, float* dw, float* db, int M,
+                        int n, int K, int plane, srlz_stream_t stream);
+/* out[M,K] = z[M,n] . W[K,n]^T + b — nn.Linear(h, input_dim) of autoencoders.py:19,59, vae.py:29 (the decoded frames). */
+int srlz_dense_out_fwd(const float* z, const float* w, const float* b, float* out, int M, int n, int K, int plane,
+                       srlz_stream_t stream);
+/* The same layer with the reconstruction / generation loss (losses.py:172-214) in the epilogue instead of the frames:
+ * partial[2][workgroups] fp64 sums of (out - target)^2 over rows < half (frame 0) and rows >= half (frame 1), for
+ * srlz_pair_loss_finalize. */
+int srlz_dense_out_fwd_loss_workgroups(int M, int K);
+int srlz_dense_out_fwd_loss(const float* z, const float* w, const float* b, const float* target, const uint8_t* target_u8,
+                            const float* norm_lut, double* partial, int M, int n, int K, int plane, int half, srlz_stream_t stream);
+/* Backward of that loss: dOut = ((gain[0] / div) * 2) * (z W^T + b - target) recomputed, then dw[K,n] = dOut^T . z,
+ * db[K] = column sums of dOut and (dz non-NULL) dz[M,n] = dOut . W.  ws: srlz_dense_out_bwd_workspace bytes. */
+size_t srlz_dense_out_bwd_workspace(int M, int n, int K);
+int srlz_dense_out_bwd(const float* z, const float* w, const float* b, const float* target, const uint8_t* target_u8,
+                       const float* norm_lut, const float* gain, float div, float* dz, float* dw, float* db, int M, int n, int K,
+                       int plane, void* ws, size_t ws_bytes, srlz_stream_t stream);
+/* The same gradients from a given dOut [M,K] (the materialised route: any loss of the decoded frames).  ws: at least
+ * srlz_dense_in_workspace(M, n, K) bytes. */
+int srlz_dense_out_bwd_from(const float* dout, const float* z, const float* w, float* dz, float* dw, float* db, int M, int n, int K,
+                            int plane, void* ws, size_t ws_bytes, srlz_stream_t stream);
+/* nn.Tanh of the dense auto-encoder (autoencoders.py:52-62): y = tanh(x); dx = (1 - y^2) * dy. */
+int srlz_tanh_fwd(const float* x, float* y, int n, srlz_stream_t stream);
+int srlz_tanh_bwd(const float* y, const float* dy, float* dx, int n, srlz_stream_t stream);
+/* out = a + b — GaussianNoiseVariant's x + noise (custom_layers.py:49-50). */
+int srlz_add_f32(const float* a, const float* b, float* out, int n, srlz_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Linear layers — nn.Linear: autoencoders.py:94-100, vae.py:52-57, forward_inverse.py:16,48-55.
  * y[M,N] = x[M,K] . w[N,K]^T + b[N]   (w in torch [out,in] layout), optional ReLU on y.
  * ------------------------------------------------------------------------------------------------------------ */

@@ -359,11 +359,12 @@ class SRL4robotics(BaseLearner):
         """True when the ONLY readers of the step's observations are the first convolution (forward and weight gradient) and the
         reconstruction / generation loss inside the last ConvTranspose — the kernels that take the loader's uint8 frames as they
         are (ops.EncInFn / ops.DecOutLossFn): the default AE / VAE steps and the heads-only steps (inverse / forward / reward on the
-        CustomCNN encoder) of the custom_cnn models.  Everything else
+        CustomCNN encoder) of the custom_cnn models — and the same steps of the mlp / linear models, whose wide input layer and fused
+        reconstruction loss read the bytes the same way (ops.DenseInFn / ops.DenseOutLossFn).  Everything else
         (DAE noise, perceptual loss, triplets, the ResNet trunks, graph replay, the A/B switches that undo those fusions) gets the
         normalised float tensor (ops.frames_as_float)."""
         from srlz import hotpath
-        return (RAW_UINT8_INPUT and self.model_type == "custom_cnn" and self._use_pair
+        return (RAW_UINT8_INPUT and self.model_type in ("custom_cnn", "mlp", "linear") and self._use_pair
                 and not self._use_graph and not self.use_triplets and not self.use_dae
                 and not (self.use_vae and self.perceptual_similarity_loss)
                 and hotpath._FUSE_RECON and hotpath._FUSE_ENC_IN and hotpath.TAPS is None)

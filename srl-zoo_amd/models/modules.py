@@ -1,11 +1,16 @@
 """SRLModules — one encoder chosen by (model_type, losses) + forward / inverse / reward heads
 (reference models/modules.py:17-100) and SRLModulesSplit, the split-representation variant (modules.py:103-288).
-Only the conv family (`custom_cnn`) is on the MI355X hot path."""
+On the MI355X hot path: the conv family (`custom_cnn`) and the dense models of `mlp` / `linear` (SRLModules only)."""
 from __future__ import print_function, division, absolute_import
 
 from srlz import ops
-from .autoencoders import CNNAutoEncoder
-from .vae import CNNVAE
+try:
+    from preprocessing.preprocess import getInputDim
+except ImportError:  # imported as a sub-package from another repository
+    from ..preprocessing.preprocess import getInputDim
+from .autoencoders import CNNAutoEncoder, DenseAutoEncoder, LinearAutoEncoder
+from .vae import CNNVAE, DenseVAE
+from .priors import SRLDenseNetwork, SRLLinear
 from .triplet import EmbeddingNet
 from .forward_inverse import BaseForwardModel, BaseInverseModel, BaseRewardModel
 from .models import *  # noqa: F401,F403  (BaseModelSRL, CustomCNN, encodeOneHot, ... as in the reference)
@@ -21,7 +26,33 @@ def _forward_pair(module, x, next_x):
 
 
 OUT_OF_SCOPE = "model_type '{}' / losses {} are outside the MI355X hot path of this build (custom_cnn with " \
-               "autoencoder | vae | dae | inverse | forward | reward | perceptual | triplet); use the reference implementation for them"
+               "autoencoder | vae | dae | inverse | forward | reward | perceptual | triplet; mlp / linear without split, perceptual or " \
+               "triplet); use the reference implementation for them"
+
+
+def _dense_model(model_type, losses, state_dim, cuda):
+    """The model of `--model-type mlp | linear` (reference modules.py:53-69), or NotImplementedError for the combinations that have
+    no behaviour to reproduce here."""
+    if "perceptual" in losses:
+        raise NotImplementedError("model_type '%s' with the perceptual loss: the denoiser's states of the reconstructions are a "
+                                  "custom_cnn-only route in this build" % model_type)
+    if "triplet" in losses:
+        raise NotImplementedError("model_type '%s' with triplets: the reference replaces the model by the ResNet-18 EmbeddingNet "
+                                  "(modules.py:71-73); use model_type custom_cnn" % model_type)
+    ae = "autoencoder" in losses or "dae" in losses
+    if model_type == "linear" and not ae and "vae" in losses:
+        raise NotImplementedError("model_type 'linear' with 'vae': the reference builds SRLLinear (modules.py:66-69) and then fails "
+                                  "to unpack its output as (decoded, mu, logvar)")
+    input_dim = getInputDim()
+    if model_type == "mlp":
+        if ae:
+            return DenseAutoEncoder(input_dim=input_dim, state_dim=state_dim)
+        if "vae" in losses:
+            return DenseVAE(input_dim=input_dim, state_dim=state_dim)
+        return SRLDenseNetwork(input_dim, state_dim, cuda=cuda)
+    if ae:
+        return LinearAutoEncoder(input_dim=input_dim, state_dim=state_dim)
+    return SRLLinear(input_dim=input_dim, state_dim=state_dim, cuda=cuda)
 
 
 class SRLModules(BaseForwardModel, BaseInverseModel, BaseRewardModel):
@@ -47,6 +78,9 @@ class SRLModules(BaseForwardModel, BaseInverseModel, BaseRewardModel):
         self.initInverseNet(state_dim, action_dim, model_type=inverse_model_type)
         self.initRewardNet(state_dim)
 
+        if model_type in ("mlp", "linear"):
+            self.model = _dense_model(model_type, self.losses, state_dim, cuda)
+            return
         if model_type != "custom_cnn":
             raise NotImplementedError(OUT_OF_SCOPE.format(model_type, self.losses))
         if "autoencoder" in self.losses or "dae" in self.losses:
@@ -63,6 +97,8 @@ class SRLModules(BaseForwardModel, BaseInverseModel, BaseRewardModel):
         return self.model.getStates(observations)
 
     def forward(self, x):
+        if self.model_type in ("linear", "mlp"):
+            x = x.contiguous()  # (reference modules.py:83-85)
         return self.model(x)
 
     def forwardPair(self, x, next_x):
@@ -134,6 +170,9 @@ class SRLModulesSplit(BaseForwardModel, BaseInverseModel, BaseRewardModel):
 
         if model_type == "resnet":
             raise ValueError("Resnet not supported when splitting representation")
+        if model_type in ("mlp", "linear"):
+            raise NotImplementedError("model_type '%s' with a split representation: SRLModulesSplit's encode / decode / "
+                                      "detachSplit routes are built for the conv models only" % model_type)
         if model_type != "custom_cnn":
             raise NotImplementedError(OUT_OF_SCOPE.format(model_type, self.losses))
         if "autoencoder" in losses or "dae" in losses:

@@ -147,6 +147,19 @@ _PROTOS = {
     "srlz_bn_relu_bwd": (c_int, [P, P, P, P, P, P, c_int, P, c_size_t, c_longlong, c_int, P]),
     "srlz_nchw_to_nhwc": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
     "srlz_nhwc_to_nchw": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
+    "srlz_dense_supported": (c_int, [c_int, c_int, c_int, c_int]),
+    "srlz_dense_in_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "srlz_dense_in_fwd": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
+    "srlz_dense_in_wgrad": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
+    "srlz_dense_out_fwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
+    "srlz_dense_out_fwd_loss_workgroups": (c_int, [c_int, c_int]),
+    "srlz_dense_out_fwd_loss": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
+    "srlz_dense_out_bwd_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "srlz_dense_out_bwd": (c_int, [P, P, P, P, P, P, P, c_float, P, P, P, c_int, c_int, c_int, c_int, P, c_size_t, P]),
+    "srlz_dense_out_bwd_from": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, c_size_t, P]),
+    "srlz_tanh_fwd": (c_int, [P, P, c_int, P]),
+    "srlz_tanh_bwd": (c_int, [P, P, P, c_int, P]),
+    "srlz_add_f32": (c_int, [P, P, P, c_int, P]),
     "srlz_linear_workspace": (c_size_t, [c_int, c_int, c_int]),
     "srlz_linear_fwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, c_size_t, P]),
     "srlz_linear_bwd_data": (c_int, [P, P, P, c_int, c_int, c_int, P, c_size_t, P]),
@@ -194,7 +207,8 @@ _NOT_STATUS = {"srlz_version", "srlz_device_cus", "srlz_conv64_fwd_tiles", "srlz
                "srlz_convT_out_bwd_fused_supported",
                "srlz_conv64_bwd_data_tiles", "srlz_conv64_bwd_fused_bn_rows", "srlz_conv64_wino_supported", "srlz_conv64_wino_packed_floats",
                "srlz_conv64_wino_tiles", "srlz_conv64_wino_bwd_data_rows",
-               "srlz_conv64_debug_program", "srlz_comm_world"}
+               "srlz_conv64_debug_program", "srlz_comm_world", "srlz_dense_supported",
+               "srlz_dense_out_fwd_loss_workgroups"}
 
 EXPORTED = sorted(_PROTOS.keys())
 

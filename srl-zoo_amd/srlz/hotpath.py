@@ -292,6 +292,42 @@ def resnet18_forward(trunk, x, training, groups=1):
     return feat
 
 
+# ---- dense layers of the mlp / linear models (reference models/autoencoders.py:6-81, vae.py:6-40, priors.py:71-125) ---------------
+def _plane(x):
+    """W * H of the image planes behind the flat index of x.view(M, -1) (a flat x: the planes of the model's 224 x 224 input)."""
+    if x.dim() == 4:
+        return x.shape[2] * x.shape[3]
+    try:
+        from preprocessing.preprocess import IMAGE_WIDTH, IMAGE_HEIGHT
+    except ImportError:  # imported as a sub-package from another repository
+        from ..preprocessing.preprocess import IMAGE_WIDTH, IMAGE_HEIGHT
+    return IMAGE_WIDTH * IMAGE_HEIGHT
+
+
+def dense_in(layer, x, act=ops.ACT_NONE):
+    """act(layer(x.view(M, -1))) for the nn.Linear(input_dim, h) of a dense model: x [M, C, W, H] fp32 or the loader's uint8 frames."""
+    require_gpu(x, "dense encoder")
+    return ops.DenseInFn.apply(x, layer.weight, layer.bias, act, _plane(x))
+
+
+def dense_out(layer, z):
+    """layer(z) [M, input_dim] for the nn.Linear(h, input_dim) of a dense auto-encoder / VAE — or, inside a recon_loss_into request
+    whose target matches, the reconstruction / generation loss in the layer's epilogue (ops.DenseOutLossFn, stored in req.loss) and
+    a zero-stride stand-in of the right shape in place of frames that were never written."""
+    req = _RECON
+    m, k = z.shape[0], layer.weight.shape[0]
+    if req is not None and req.loss is None and torch.is_grad_enabled() and m % 2 == 0 and req.target.shape[0] == m \
+            and req.target[0].numel() == k and not req.target.requires_grad:
+        # (the target's own planes: its uint8 channel is k / (W * H) of ITS layout)
+        req.loss = ops.DenseOutLossFn.apply(z, layer.weight, layer.bias, req.target, req.mean, _plane(req.target))
+        return torch.zeros((), dtype=torch.float32, device=z.device).expand(m, k)
+    return ops.DenseOutFn.apply(z, layer.weight, layer.bias, _plane(z))
+
+
+def tanh(x):
+    return ops.TanhFn.apply(x)
+
+
 def linear(layer, x, relu=False):
     return ops.LinearFn.apply(x, layer.weight, layer.bias, relu)
 

@@ -875,6 +875,201 @@ class LinearFn(Function):
         return dx, _give(w, dw), _give(ctx.params[0], db), None
 
 
+# ----------------------------------------------------------------------------------------------------------------
+# Dense layers of the mlp / linear models — nn.Linear(input_dim, h) / nn.Linear(h, input_dim), autoencoders.py:6-81,
+# vae.py:6-40, priors.py:71-125 (csrc/dense.hip).  The image side is x.view(M, -1) of [M, C, W, H] frames: fp32, or the
+# loader's planar uint8 bytes normalised inside the kernels (same table as frames_as_float, same values bit for bit).
+# ----------------------------------------------------------------------------------------------------------------
+ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
+
+
+def _dense_image(x, name):
+    """(fp32 tensor or None, uint8 tensor or None, M, K) of an image operand [M, C, W, H] (or an fp32 [M, K])."""
+    if is_u8_frames(x):
+        x = _check_u8(x, name)
+        return None, x, x.shape[0], x[0].numel()
+    x = _check(x, name)
+    return x, None, x.shape[0], x[0].numel()
+
+
+def _dense_require(m, n, k, plane):
+    if not C.dense_supported(m, n, k, plane):
+        raise C.SrlzError("dense layer M = %d, n = %d, K = %d (plane %d): %s" % (m, n, k, plane, C.error_text()))
+
+
+def _dense_flop(m, n, k):
+    return 2.0 * m * n * k
+
+
+class DenseInFn(Function):
+    """y[M,n] = act(x.view(M, -1) . W^T + b) with act none / ReLU / tanh; backward: the weight and bias gradients only (the images
+    carry no gradient in these models)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, act, plane):
+        if x.requires_grad:
+            raise C.SrlzError("dense input layer: the image operand must not require a gradient (no data-gradient kernel)")
+        xf, x8, m, k = _dense_image(x, "dense input")
+        w = _check(w, "dense weight")
+        n = w.shape[0]
+        if w.shape[1] != k:
+            raise C.SrlzError("dense input layer: weight %s does not match K = %d" % (tuple(w.shape), k))
+        _dense_require(m, n, k, plane)
+        y = torch.empty((m, n), dtype=torch.float32, device=w.device)
+        nbytes = C.dense_in_workspace(m, n, k)
+        ws = _ws(nbytes, w.device)
+        lut = norm_lut(w.device) if x8 is not None else None
+        _launch("dense_tile_kernel", "in_fwd m%d n%d k%d%s" % (m, n, k, " u8" if x8 is not None else ""), _dense_flop(m, n, k),
+                lambda: C.dense_in_fwd(ptr(xf), ptr(x8), ptr(lut), ptr(w), ptr(b), ptr(y), m, n, k, plane, act, ptr(ws), nbytes,
+                                       stream()))
+        ctx.save_for_backward(xf if xf is not None else x8, w, y if act != ACT_NONE else None)
+        ctx.u8, ctx.act, ctx.plane, ctx.has_bias = x8 is not None, act, plane, b is not None
+        ctx.params = (b,)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, y = ctx.saved_tensors
+        dy = _check(dy, "dense dy")
+        m, n, k = x.shape[0], w.shape[0], w.shape[1]
+        if ctx.act == ACT_RELU:
+            dy = dy.clone()
+            C.relu_bwd_inplace(ptr(y), ptr(dy), dy.numel(), stream())
+        elif ctx.act == ACT_TANH:
+            d = torch.empty_like(dy)
+            C.tanh_bwd(ptr(y), ptr(dy), ptr(d), dy.numel(), stream())
+            dy = d
+        dw = _gbuf(w)
+        db = _gbuf(ctx.params[0]) if ctx.has_bias else None
+        xf, x8 = (None, x) if ctx.u8 else (x, None)
+        lut = norm_lut(w.device) if ctx.u8 else None
+        _launch("dense_tile_kernel", "in_wgrad m%d n%d k%d%s" % (m, n, k, " u8" if ctx.u8 else ""), _dense_flop(m, n, k),
+                lambda: C.dense_in_wgrad(ptr(dy), ptr(xf), ptr(x8), ptr(lut), ptr(dw), ptr(db), m, n, k, ctx.plane, stream()))
+        return None, _give(w, dw), _give(ctx.params[0], db), None, None
+
+
+def _dense_out_grads(ctx, z, w, m, n, k, nbytes, call):
+    """Shared tail of the two backward passes of the output layer: buffers (a workspace of nbytes), then `call(dz, dw, db, ws, nbytes)`."""
+    dz = torch.empty((m, n), dtype=torch.float32, device=z.device) if ctx.needs_input_grad[0] else None
+    dw = _gbuf(w)
+    b = ctx.params[0]
+    db = _gbuf(b) if b is not None else torch.empty(k, dtype=torch.float32, device=z.device)
+    # (a per-call buffer, not a grow-only slot: the dOut staging of the fused route is M * K floats, and the allocator may hand it
+    # to the next layer's backward as soon as this launch sequence is enqueued)
+    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=z.device)
+    _launch("dense_tile_kernel", "out_bwd m%d n%d k%d" % (m, n, k), 3 * _dense_flop(m, n, k), lambda: call(dz, dw, db, ws, nbytes))
+    return dz, _give(w, dw), (_give(b, db) if b is not None else None)
+
+
+class DenseOutFn(Function):
+    """out[M,K] = z . W^T + b — the decoded frames, flat (the caller views them as [M, C, W, H])."""
+
+    @staticmethod
+    def forward(ctx, z, w, b, plane):
+        z, w = _check(z, "dense output input"), _check(w, "dense output weight")
+        m, n = z.shape
+        k = w.shape[0]
+        if w.shape[1] != n:
+            raise C.SrlzError("dense output layer: weight %s does not match n = %d" % (tuple(w.shape), n))
+        _dense_require(m, n, k, plane)
+        out = torch.empty((m, k), dtype=torch.float32, device=z.device)
+        _launch("dense_tile_kernel", "out_fwd m%d n%d k%d" % (m, n, k), _dense_flop(m, n, k),
+                lambda: C.dense_out_fwd(ptr(z), ptr(w), ptr(b), ptr(out), m, n, k, plane, stream()))
+        ctx.save_for_backward(z, w)
+        ctx.plane = plane
+        ctx.params = (b,)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        z, w = ctx.saved_tensors
+        dout = _check(dout, "dense output grad")
+        m, n = z.shape
+        k = w.shape[0]
+        # (the given dOut needs no staging: only the data gradient's split partials)
+        return _dense_out_grads(ctx, z, w, m, n, k, C.dense_in_workspace(m, n, k), lambda dz, dw, db, ws, nbytes: C.dense_out_bwd_from(
+            ptr(dout), ptr(z), ptr(w), ptr(dz), ptr(dw), ptr(db), m, n, k, ctx.plane, ptr(ws), nbytes, stream())) + (None,)
+
+
+class DenseOutLossFn(Function):
+    """The output layer AND the step's reconstruction (mean=True: sum / numel per frame, added) or generation (sums added) loss
+    against target [M, C, W, H] (fp32 or uint8 frames; M = the two frames of a step) as one node: the decoded frames are never
+    written.  Backward: d(loss)/d(out) = ((upstream / div) * 2) * (out - target) recomputed inside the backward kernels."""
+
+    @staticmethod
+    def forward(ctx, z, w, b, target, mean, plane):
+        z, w = _check(z, "dense output input"), _check(w, "dense output weight")
+        tf, t8, mt, kt = _dense_image(target, "reconstruction target")
+        m, n = z.shape
+        k = w.shape[0]
+        if w.shape[1] != n or mt != m or kt != k or m % 2:
+            raise C.SrlzError("fused dense reconstruction loss: target %s does not match the output [%d, %d]"
+                              % (tuple(target.shape), m, k))
+        _dense_require(m, n, k, plane)
+        nwg = C.dense_out_fwd_loss_workgroups(m, k)
+        part = _ws(2 * nwg * 8, z.device, slot=2)
+        lut = norm_lut(z.device) if t8 is not None else None
+        _launch("dense_tile_kernel", "out_fwd+loss m%d n%d k%d%s" % (m, n, k, " u8" if t8 is not None else ""), _dense_flop(m, n, k),
+                lambda: C.dense_out_fwd_loss(ptr(z), ptr(w), ptr(b), ptr(tf), ptr(t8), ptr(lut), ptr(part), m, n, k, plane, m // 2,
+                                             stream()))
+        sums = torch.empty(2, dtype=torch.float32, device=z.device)
+        comb = torch.empty((), dtype=torch.float32, device=z.device)
+        per_frame = (m // 2) * k
+        C.pair_loss_finalize(ptr(part), nwg, per_frame, 1 if mean else 0, ptr(sums), ptr(comb), stream())
+        ctx.save_for_backward(z, w, tf if tf is not None else t8)
+        ctx.u8, ctx.plane, ctx.div = t8 is not None, plane, float(per_frame) if mean else 1.0
+        ctx.params = (b,)
+        return comb
+
+    @staticmethod
+    def backward(ctx, g):
+        z, w, t = ctx.saved_tensors
+        g = _check(g, "loss grad")
+        m, n = z.shape
+        k = w.shape[0]
+        tf, t8 = (None, t) if ctx.u8 else (t, None)
+        lut = norm_lut(z.device) if ctx.u8 else None
+        b = ctx.params[0]
+        return _dense_out_grads(ctx, z, w, m, n, k, C.dense_out_bwd_workspace(m, n, k), lambda dz, dw, db, ws, nbytes: C.dense_out_bwd(
+            ptr(z), ptr(w), ptr(b), ptr(tf), ptr(t8), ptr(lut), ptr(g), ctx.div, ptr(dz), ptr(dw), ptr(db), m, n, k, ctx.plane,
+            ptr(ws), nbytes, stream())) + (None, None, None)
+
+
+class TanhFn(Function):
+    """nn.Tanh (autoencoders.py:52-62)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = _check(x, "tanh input")
+        y = torch.empty_like(x)
+        C.tanh_fwd(ptr(x), ptr(y), x.numel(), stream())
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        y, = ctx.saved_tensors
+        dy = _check(dy, "tanh dy")
+        dx = torch.empty_like(dy)
+        C.tanh_bwd(ptr(y), ptr(dy), ptr(dx), dy.numel(), stream())
+        return dx
+
+
+class AddConstFn(Function):
+    """x + c for a constant tensor c (GaussianNoiseVariant's x + noise, custom_layers.py:49-50); the gradient passes through."""
+
+    @staticmethod
+    def forward(ctx, x, c):
+        x, c = _check(x, "add input"), _check(c, "add constant")
+        out = torch.empty_like(x)
+        C.add_f32(ptr(x), ptr(c), ptr(out), x.numel(), stream())
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        return dy, None
+
+
 class TotalLossFn(Function):
     """total = sum_i w_i * l_i over 0-dim device scalars, as LossManager.computeTotalLoss forms it (reference losses/losses.py:55-56:
     Python's left-to-right sum of separately rounded fp32 products), in ONE launch that also drops [total, l_0, l_1, ...] into

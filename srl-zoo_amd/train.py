@@ -3,8 +3,9 @@ driving the MI355X-native SRL4robotics.  Multi-GPU: launch one process per GPU w
 ``python -m torch.distributed.run --nproc-per-node N train.py ...`` (RANK / LOCAL_RANK / WORLD_SIZE are read from the
 environment; backend "nccl" is RCCL on ROCm).
 
-Out of scope of this build (rejected with a clear message): --model-type other than custom_cnn, the losses of other
-SRL methods (priors, triplet, episode-prior, reward-prior), plots.
+--model-type custom_cnn, mlp and linear run (mlp / linear without a split representation, perceptual or triplet).
+Out of scope of this build (rejected with a clear message): --model-type resnet, the losses of other SRL methods (priors,
+episode-prior, reward-prior), plots.
 """
 from __future__ import print_function, division, absolute_import
 
@@ -62,7 +63,7 @@ def buildParser():
             parser.add_argument(*names, type=kind, default=default, help="%s (default: %r)" % (text, default),
                                 required=(names[0] == "--data-folder"))
     parser.add_argument('--model-type', type=str, default="custom_cnn", choices=['custom_cnn', 'resnet', 'mlp', 'linear'],
-                        help='encoder family; only custom_cnn runs here')
+                        help='encoder family; custom_cnn, mlp and linear run here')
     parser.add_argument('--inverse-model-type', type=str, default="linear", choices=['mlp', 'linear'],
                         help='architecture of the inverse model')
     parser.add_argument('--losses', nargs='+', default=["inverse"], **parseLossArguments(

@@ -69,7 +69,7 @@ def digest_state_dict(sd):
                 sums=np.array(sums), abss=np.array(abss))
 
 
-def build(th, ref_pre, SRLModules, losses, S=200, A=6, C=3, seed=1, inverse="linear", split=None):
+def build(th, ref_pre, SRLModules, losses, S=200, A=6, C=3, seed=1, inverse="linear", split=None, model_type="custom_cnn"):
     ref_pre.N_CHANNELS = C
     np.random.seed(seed)
     th.manual_seed(seed)
@@ -77,7 +77,7 @@ def build(th, ref_pre, SRLModules, losses, S=200, A=6, C=3, seed=1, inverse="lin
         from models.modules import SRLModulesSplit  # the reference's
         return SRLModulesSplit(state_dim=S, action_dim=A, cuda=False, model_type="custom_cnn", losses=losses,
                                split_dimensions=split, inverse_model_type=inverse)
-    return SRLModules(state_dim=S, action_dim=A, cuda=False, model_type="custom_cnn",
+    return SRLModules(state_dim=S, action_dim=A, cuda=False, model_type=model_type,
                       losses=losses, inverse_model_type=inverse)
 
 
@@ -97,12 +97,13 @@ def bn_digest(model, out, prefix="bn/"):
 
 
 def step_case(th, ref_pre, SRLModules, RL, losses, B, C=3, S=200, A=6, n_steps=1, lr=None,
-              eps_seed=99, beta=1.0, inverse="linear", weights=None, split=None, l1_reg=0.0, l2_reg=0.0, val_steps=()):
+              eps_seed=99, beta=1.0, inverse="linear", weights=None, split=None, l1_reg=0.0, l2_reg=0.0, val_steps=(),
+              model_type="custom_cnn"):
     """One (or several) loop bodies of models/learner.py:373-497 driven on the reference classes.
     `val_steps`: steps run as validation minibatches (learner.py:362-364,487-497: eval mode, forward + backward, no
     optimizer step)."""
     model = build(th, ref_pre, SRLModules, [l for l in losses if l != "perceptual"] if split is None else losses, S=S, A=A,
-                  C=C, inverse=inverse, split=split)
+                  C=C, inverse=inverse, split=split, model_type=model_type)
     denoiser = None
     if "perceptual" in losses:  # the frozen, eval-mode DAE of learner.py:317-326 (seed 7 stands in for "pre-trained")
         denoiser = build(th, ref_pre, SRLModules, ["dae"], S=S, A=A, C=C, seed=7)
@@ -209,6 +210,12 @@ def step_case(th, ref_pre, SRLModules, RL, losses, B, C=3, S=200, A=6, n_steps=1
         st = model.getStates(th.from_numpy(obs))
     out["eval_states/full"] = st.double().numpy()
     return out
+
+
+def dense_subs(out):
+    """Every */sub array of a digest thinned to at most 4096 samples, v[::ceil(len / 4096)] (tests/test_dense_step_gpu.py takes the
+    same samples): the dense models' gradients and reconstructions have up to 60 M elements."""
+    return {k: (v[::max(1, -(-len(v) // 4096))] if k.endswith("/sub") else v) for k, v in out.items()}
 
 
 def layer_trace(th, ref_pre, SRLModules):
@@ -344,7 +351,7 @@ def _install_cv2_shim():
     cv2.INTER_AREA, cv2.COLOR_BGR2RGB = 3, 4
 
 
-def loop_case(th, losses, n_epochs=2, bs=8, S=12, seed=3, lr=1e-4, n_episodes=4, ep_len=26, **ctor):
+def loop_case(th, losses, n_epochs=2, bs=8, S=12, seed=3, lr=1e-4, n_episodes=4, ep_len=26, model_type="custom_cnn", **ctor):
     """The UNMODIFIED SRL4robotics.learn() (models/learner.py:259-579: forked loader process, queue, train/validation
     split, best-model checkpoint, state prediction) on the tiny generated dataset of tests/dataset_util.py."""
     import tempfile
@@ -359,7 +366,7 @@ def loop_case(th, losses, n_epochs=2, bs=8, S=12, seed=3, lr=1e-4, n_episodes=4,
         os.chdir(tmp)
         os.makedirs("logs/run", exist_ok=True)
         RLn.DISPLAY_PLOTS, RLn.N_EPOCHS, RLn.BATCH_SIZE, RLn.VALIDATION_SIZE = False, n_epochs, bs, 0.2
-        srl = RLn.SRL4robotics(S, model_type="custom_cnn", seed=seed, learning_rate=lr, cuda=False, losses=losses,
+        srl = RLn.SRL4robotics(S, model_type=model_type, seed=seed, learning_rate=lr, cuda=False, losses=losses,
                                n_actions=6, log_folder="logs/run", **ctor)
         loss_history, states, pairs = srl.learn(paths, actions, rewards, starts)
         out = {"states/full": np.asarray(states, dtype=np.float64),
@@ -368,8 +375,10 @@ def loop_case(th, losses, n_epochs=2, bs=8, S=12, seed=3, lr=1e-4, n_episodes=4,
                "history/values": np.array([loss_history[k] for k in sorted(loss_history.keys())], dtype=np.float64)}
         sd = digest_state_dict(th.load("logs/run/srl_model.pth"))
         out["final/names"], out["final/sums"], out["final/abss"] = sd["names"], sd["sums"], sd["abss"]
-        out["config"] = np.array(json.dumps(dict(losses=losses, n_epochs=n_epochs, bs=bs, S=S, seed=seed, lr=lr,
-                                                 n_episodes=n_episodes, ep_len=ep_len, ctor=ctor)))
+        cfg = dict(losses=losses, n_epochs=n_epochs, bs=bs, S=S, seed=seed, lr=lr, n_episodes=n_episodes, ep_len=ep_len, ctor=ctor)
+        if model_type != "custom_cnn":  # (the conv cases' config strings stay byte-identical)
+            cfg["model_type"] = model_type
+        out["config"] = np.array(json.dumps(cfg))
         return out
     finally:
         os.chdir(cwd)
@@ -379,7 +388,10 @@ def loop_case(th, losses, n_epochs=2, bs=8, S=12, seed=3, lr=1e-4, n_episodes=4,
 # whole-loop cases run in a FRESH interpreter each: learn() forks its loader processes, and a child forked from a parent
 # that has already run OpenMP-parallel torch code dead-locks in its first parallel region
 LOOP_CASES = {"loop_aeif": dict(losses=["autoencoder", "inverse", "forward"]),
-              "loop_ae_reward": dict(losses=["autoencoder", "reward"], n_epochs=1, seed=5, l2_reg=1e-4)}
+              "loop_ae_reward": dict(losses=["autoencoder", "reward"], n_epochs=1, seed=5, l2_reg=1e-4),
+              # --model-type mlp / linear (reference modules.py:53-69)
+              "loop_mlp_ae": dict(losses=["autoencoder"], model_type="mlp"),
+              "loop_linear_aeif": dict(losses=["autoencoder", "inverse", "forward"], model_type="linear")}
 
 
 def run_loop_child(name):
@@ -419,6 +431,11 @@ def main():
     for tag, losses, C in (("ae_c3", ["autoencoder"], 3), ("vae_c3", ["vae"], 3), ("ae_c6", ["autoencoder"], 6),
                            ("cnn_c3", ["inverse"], 3)):
         save("init_" + tag, lambda: digest_state_dict(build(th, ref_pre, SRLModules, losses, C=C).state_dict()))
+    # (1b) the dense models of --model-type mlp / linear (reference modules.py:53-69)
+    for tag, mt, losses, C in (("mlp_ae_c3", "mlp", ["autoencoder"], 3), ("mlp_vae_c3", "mlp", ["vae"], 3),
+                               ("mlp_net_c3", "mlp", ["inverse", "forward"], 3), ("linear_ae_c3", "linear", ["autoencoder"], 3),
+                               ("linear_net_c3", "linear", ["inverse", "forward"], 3), ("mlp_ae_c6", "mlp", ["autoencoder"], 6)):
+        save("init_" + tag, lambda: digest_state_dict(build(th, ref_pre, SRLModules, losses, C=C, model_type=mt).state_dict()))
     # (2) single train-mode steps
     save("step_ae_b2", lambda: step_case(th, ref_pre, SRLModules, RL, ["autoencoder"], B=2))
     save("step_ae_b4", lambda: step_case(th, ref_pre, SRLModules, RL, ["autoencoder"], B=4))
@@ -470,6 +487,17 @@ def main():
     # gradient, near-zero gradient elements (the ones Adam turns into +-lr steps of arbitrary sign) are far rarer than at B = 2,
     # so a free-running end point can be held much tighter (tests/test_trajectory_gpu.py, tools/measure_spread.py)
     save("trace10_ae_b32", lambda: step_case(th, ref_pre, SRLModules, RL, ["autoencoder"], B=32, n_steps=10, lr=1e-4))
+    # (7) the dense models of --model-type mlp / linear (their image-sized tensors keep at most 4096 strided samples: dense_sub()): single steps, Adam traces (one with the l1 / l2 regularisers, which reach
+    # the conv stacks these models build but never run)
+    for tag, mt, losses, C in (("mlp_ae", "mlp", ["autoencoder"], 3), ("mlp_dae", "mlp", ["dae"], 3), ("mlp_vae", "mlp", ["vae"], 3),
+                               ("linear_ae", "linear", ["autoencoder"], 3), ("mlp_if", "mlp", ["inverse", "forward"], 3),
+                               ("linear_if", "linear", ["inverse", "forward"], 3), ("mlp_ae_c6", "mlp", ["autoencoder"], 6)):
+        save("step_%s_b2" % tag, lambda: dense_subs(step_case(th, ref_pre, SRLModules, RL, losses, B=2, C=C, model_type=mt)))
+    for tag, mt, losses in (("mlp_ae", "mlp", ["autoencoder"]), ("mlp_vae", "mlp", ["vae"]), ("linear_ae", "linear", ["autoencoder"])):
+        save("trace_%s_b2" % tag, lambda: dense_subs(step_case(th, ref_pre, SRLModules, RL, losses, B=2, n_steps=3, lr=1e-4,
+                                                               model_type=mt)))
+    save("trace_mlp_ae_l1l2_b2", lambda: dense_subs(step_case(th, ref_pre, SRLModules, RL, ["autoencoder"], B=2, n_steps=3, lr=1e-4,
+                                                              l1_reg=1e-5, l2_reg=1e-4, model_type="mlp")))
     for lname in LOOP_CASES:
         save(lname, lambda: run_loop_child(lname))
 
