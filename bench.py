@@ -7,7 +7,7 @@ is already resident in HBM: forward of obs and next_obs through the conv auto-en
 BASELINE.json configs[1]: synthetic 224x224x3 observations, --losses autoencoder, custom_cnn, state-dim 200, bs=256.
 `--losses vae` / `--losses autoencoder inverse forward` select configs[2] / configs[3]'s per-GPU workload.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 N > 1 runs one process per GPU over RCCL.  Either a launcher provides the ranks (python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* are read from the environment), or — when
@@ -15,6 +15,10 @@ WORLD_SIZE is not set — bench.py starts the N ranks itself (self_launch) and r
 
 Prints ONE JSON line (rank 0).  value = 2*B*N*K / t  (both frames of a sample go through forward+backward), with t the
 max over ranks of the wall time of exactly K steps bracketed by barrier + synchronize.
+A plain run does only what that line's headline needs: set-up, W warm-up steps, the K timed steps, the dump (--dump-outputs) and
+the line.  `--full` adds everything else the benchmark measures, each behind the timed region: the instrumented pass of
+"roofline" / "north_star", the VAE leg ("vae"), the strong-scaling leg and the all-reduce timing at N > 1 ("strong", "allreduce")
+and "cpu_baseline".  The VAE leg also runs without --full when --dump-outputs is given: the dump holds its arrays (vae_*).
 "roofline" is measured live with HIP events on the stream the kernels are launched on, for the MFMA implicit-GEMM convolution
 kernel (conv64_fwd_kernel), in a short instrumented pass of the same steps RIGHT AFTER the timed region (two events per launch
 inside the timed region cost ~0.5 % of the headline, VERDICT r2 item 11 — the timed region carries no instrumentation);
@@ -98,7 +102,7 @@ def cpu_baseline(losses, full=False):
     """The CPU oracle (oracle/torch_twin.py: the reference's own torch CPU ops, fp32, pinned to the reference by the golden
     fixtures) timed on this box's host cores with BASELINE.md section 3's protocol: the same train step (forward x2, losses,
     backward, Adam); bs = 32 (BASELINE.json configs[0]'s minibatch) with all usable cores, 3 warm-up + 10 timed steps, median —
-    that is `value`; plus a bs = 256 leg (configs[1]'s minibatch).  Default run: the bs = 256 leg is BOUNDED to 1 warm-up + 2
+    that is `value`; plus a bs = 256 leg (configs[1]'s minibatch).  `--full` alone: the bs = 256 leg is BOUNDED to 1 warm-up + 2
     timed steps (a step takes seconds; the whole leg stays within ~40 s of CPU work) and the 8-thread comparability leg is
     skipped; `--cpu-baseline-full` runs every leg of the protocol (3 + 10 steps at bs = 32 with all cores and with 8 threads,
     3 + 10 at bs = 256: minutes).  kind = "port": a restatement of the reference path, not the reference's own files (those
@@ -287,12 +291,17 @@ def main():
     ap.add_argument("--channels", type=int, default=3, choices=[3, 6, 9],
                     help="input channels: 6 = --multi-view (two stacked cameras, BASELINE.json configs[4] `vae` half); "
                          "`--losses triplet` forces 9 (anchor / positive / negative views, configs[4] `triplet` half)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the roofline / north_star instrumented pass, the VAE leg, the strong-scaling leg and "
+                         "all-reduce timing (N > 1) and the CPU baseline (the --no-* / --timer-steps / --cpu-baseline-full switches "
+                         "below refine what --full runs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline object")
     ap.add_argument("--cpu-baseline-full", action="store_true",
-                    help="every leg of BASELINE.md section 3's CPU protocol (minutes) instead of the bounded default")
+                    help="with --full: every leg of BASELINE.md section 3's CPU protocol (minutes) instead of the bounded default")
     ap.add_argument("--timer-steps", type=int, default=10,
-                    help="instrumented steps (HIP events around every MFMA launch) run AFTER the timed region for the roofline object")
-    ap.add_argument("--no-kernel-timers", action="store_true")
+                    help="with --full: instrumented steps (HIP events around every MFMA launch) run AFTER the timed region for the "
+                         "roofline object")
+    ap.add_argument("--no-kernel-timers", action="store_true", help="with --full: no instrumented pass (no roofline / north_star)")
     ap.add_argument("--host-input", action="store_true",
                     help="NOT the contract's metric: every step starts from uint8 frames [B,C,W,H] in pinned HOST memory (the H2D "
                          "copy inside the timed region; conv1 and the fused loss read the bytes) — the PCIe-inclusive rate "
@@ -301,10 +310,12 @@ def main():
                     help="the resident synthetic batch is the loader's uint8 frames [B,C,W,H] instead of the normalised float tensor "
                          "(what learn() feeds the step; conv1 and the fused loss read the bytes)")
     ap.add_argument("--no-vae-leg", action="store_true",
-                    help="skip the second leg of the headline metric (BASELINE.json configs[2]: --losses vae on the same shapes), which the "
-                         "default --losses autoencoder run measures in the same process right after the AE leg and reports as `vae`")
+                    help="skip the second leg of the headline metric (BASELINE.json configs[2]: --losses vae on the same shapes), which a "
+                         "--losses autoencoder run with --full or --dump-outputs measures in the same process right after the AE leg and "
+                         "reports as `vae`")
     ap.add_argument("--no-strong-leg", action="store_true",
-                    help="with --gpus N > 1: skip the strong-scaling leg (global batch = --batch-size, i.e. bs / N per GPU) reported as `strong`")
+                    help="with --full and --gpus N > 1: skip the strong-scaling leg (global batch = --batch-size, i.e. bs / N per GPU) "
+                         "reported as `strong`")
     ap.add_argument("--allow-short", action="store_true",
                     help="no warning on stderr when the timed region is shorter than 0.1 s (functional tests on tiny batches)")
     ap.add_argument("--host-input-nhwc", action="store_true",
@@ -448,7 +459,7 @@ def main():
     # the roofline's per-launch HIP-event times: the SAME steps, instrumented, after the clock has stopped
     # (two instrumented steps are discarded first: the first ~200 event pairs are created cold and their launches measured
     # 3-4 % long — 448 vs 432 us for the dominant kernel against rocprofv3's 434)
-    timer_steps = 0 if args.no_kernel_timers else max(0, args.timer_steps)
+    timer_steps = 0 if args.no_kernel_timers or not args.full else max(0, args.timer_steps)
     for phase, count in (("settle", 2 if timer_steps else 0), ("measure", timer_steps)):
         if count and rank == 0:
             ops.timers_enable(True)  # (clears what the settling steps recorded)
@@ -479,10 +490,11 @@ def main():
                     "timing": "HIP events on the launch stream around the collective, %d instrumented steps" % timer_steps}
 
     # ---- the other leg of the headline metric ("AE+VAE train step"): BASELINE.json configs[2], --losses vae (beta = 1) on the same
-    # shapes and batch, measured in this process right after the AE leg with the same warm-up / step counts
+    # shapes and batch, measured in this process right after the AE leg with the same warm-up / step counts (with --full, or when
+    # --dump-outputs asks for its arrays)
     vae = None
     if (list(args.losses) == ["autoencoder"] and channels == 3 and host_frames is None and not args.u8_resident
-            and not args.no_vae_leg):
+            and not args.no_vae_leg and (args.full or args.dump_outputs)):
         stdout, sys.stdout = sys.stdout, quiet
         try:
             srl_vae = SRL4robotics(args.state_dim, model_type="custom_cnn", seed=1, learning_rate=0.005, cuda=True, losses=["vae"],
@@ -503,7 +515,7 @@ def main():
 
     # ---- strong scaling beside weak (N > 1): the SAME global batch as the 1-GPU run, bs / N samples per GPU
     strong = None
-    if world > 1 and B % world == 0 and host_frames is None and not args.no_strong_leg:
+    if world > 1 and B % world == 0 and host_frames is None and not args.no_strong_leg and args.full:
         b = B // world
         pair = torch.cat((obs[:b], next_obs[:b]), 0)  # the two frames as the halves of one buffer, like the full batch
         s_obs, s_next, s_act = pair[:b], pair[b:], actions[:b].contiguous()
@@ -569,7 +581,7 @@ def main():
             step_tf = per_image * 2 * B / (dt / args.steps) / 1e12
             out["step_roofline"] = {"algorithmic_tflop_per_step": round(per_image * 2 * B / 1e12, 4),
                                     "achieved_tflops": round(step_tf, 2), "frac_of_fp32_mfma_peak": round(step_tf / PEAK_FP32_MFMA_TFLOPS, 4)}
-        rep = ops.timers_report()
+        rep = ops.timers_report() if timer_steps else {}
         # every instrumented kernel symbol (the MFMA launches of the step): launches, average, achieved rate, share of their time
         SYMBOL = {"conv64_fwd_kernel": "conv64_fwd_kernel<4, false>", "conv64_bwd_fused_kernel": "conv64_bwd_fused_kernel",
                   "conv64_dgrad_poolsum_kernel": "conv64_dgrad_poolsum_kernel<1>",
@@ -673,7 +685,7 @@ def main():
                                  "timing": "same instrumented pass as roofline (HIP events on the launch stream)"}
         if args.dump_outputs:
             out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, dumped)}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(list(args.losses), full=args.cpu_baseline_full)
         print(json.dumps(out))
     if world > 1:

@@ -145,7 +145,7 @@ def test_bench_self_launches_its_ranks():
         env.pop(k, None)
     env["SRLZ_DIST_BACKEND"] = "nccl" if torch.cuda.device_count() >= 2 else "gloo"
     proc = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                           "--batch-size", "8", "--timer-steps", "2", "--allow-short"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                           "--batch-size", "8", "--full", "--timer-steps", "2", "--allow-short"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                           timeout=500)
     assert proc.returncode == 0, proc.stderr.decode("utf-8", "replace")[-3000:]
     lines = [l for l in proc.stdout.decode().splitlines() if l.startswith("{")]
@@ -235,7 +235,7 @@ def _bench_ranks(n):
         env.pop(k, None)
     env["SRLZ_DIST_BACKEND"] = "nccl" if torch.cuda.device_count() >= n else "gloo"
     proc = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1",
-                           "--batch-size", "8", "--timer-steps", "2", "--allow-short", "--no-vae-leg"], env=env, stdout=subprocess.PIPE,
+                           "--batch-size", "8", "--full", "--timer-steps", "2", "--allow-short", "--no-vae-leg"], env=env, stdout=subprocess.PIPE,
                           stderr=subprocess.PIPE, timeout=800)
     assert proc.returncode == 0, proc.stderr.decode("utf-8", "replace")[-3000:]
     lines = [l for l in proc.stdout.decode().splitlines() if l.startswith("{")]
@@ -277,7 +277,7 @@ def test_bench_native_rccl_communicator():
         env.pop(k, None)
     env.update(SRLZ_DIST_BACKEND="nccl", SRLZ_COMM="rccl")
     proc = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1",
-                           "--batch-size", "8", "--timer-steps", "2", "--allow-short", "--no-vae-leg"], env=env, stdout=subprocess.PIPE,
+                           "--batch-size", "8", "--full", "--timer-steps", "2", "--allow-short", "--no-vae-leg"], env=env, stdout=subprocess.PIPE,
                           stderr=subprocess.PIPE, timeout=800)
     assert proc.returncode == 0, proc.stderr.decode("utf-8", "replace")[-3000:]
     out = json.loads([l for l in proc.stdout.decode().splitlines() if l.startswith("{")][0])

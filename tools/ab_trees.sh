@@ -6,7 +6,7 @@
 # clock: only same-box numbers mean anything.
 rounds=$1; a=$2; b=$3; shift 3
 for i in $(seq $rounds); do for t in $a $b; do
-  (cd $t && python bench.py --no-cpu-baseline "$@" 2>/dev/null | python -c "
+  (cd $t && python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 ns = d.get('north_star', {})

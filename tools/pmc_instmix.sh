@@ -1,15 +1,17 @@
 #!/bin/bash
 # usage (GPU box): tools/pmc_instmix.sh <tag> -- <command ...>
 # Two rocprofv3 PMC passes (+ kernel trace) over <command>: the dynamic instruction mix of every kernel per MFMA and the split of its
-# wave cycles into issuing / waiting for an issue slot / parked (s_waitcnt, barrier).  -> gpurun_out/instmix_<tag>.txt
+# wave cycles into issuing / waiting for an issue slot / parked (s_waitcnt, barrier).  -> $OUT_DIR/instmix_<tag>.txt (default
+# profile_out/)
 # (profiles/NOTES.md 5.3: behind fp32 MFMAs no instruction is free — this is where a kernel's non-MFMA SIMD time comes from.)
 tag=$1; shift 2
 export TMPDIR=/tmp
-mkdir -p gpurun_out
+out=${OUT_DIR:-profile_out}
+mkdir -p $out
 rm -rf /tmp/im_${tag}_a /tmp/im_${tag}_b
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_SMEM SQ_WAVE_CYCLES SQ_WAIT_ANY --kernel-trace --output-format csv -d /tmp/im_${tag}_a -o p -- "$@" > /dev/null 2>&1
 rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_BUSY_CYCLES --kernel-trace --output-format csv -d /tmp/im_${tag}_b -o p -- "$@" > /dev/null 2>&1
-python - /tmp/im_${tag}_a /tmp/im_${tag}_b > gpurun_out/instmix_${tag}.txt <<'PY'
+python - /tmp/im_${tag}_a /tmp/im_${tag}_b > $out/instmix_${tag}.txt <<'PY'
 import csv, glob, sys, collections
 acc = collections.defaultdict(lambda: collections.defaultdict(float))
 for root in sys.argv[1:3]:
@@ -44,4 +46,4 @@ for _, name, c, us, n in sorted(rows, reverse=True):
         100 * c["SQ_ACTIVE_INST_ANY"] / wc, 100 * c["SQ_ACTIVE_INST_VALU"] / wc, 100 * c["SQ_ACTIVE_INST_LDS"] / wc, 100 * c["SQ_ACTIVE_INST_SCA"] / wc,
         100 * c["SQ_ACTIVE_INST_VMEM"] / wc, 100 * c["SQ_WAIT_INST_ANY"] / wc, 100 * c["SQ_WAIT_INST_LDS"] / wc, 100 * c["SQ_WAIT_ANY"] / wc))
 PY
-cat gpurun_out/instmix_${tag}.txt
+cat $out/instmix_${tag}.txt

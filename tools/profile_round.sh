@@ -1,7 +1,8 @@
 #!/bin/bash
 # usage (on the GPU box): tools/profile_round.sh <tag> [pmc]     e.g. r02a
-# Produces under gpurun_out/<tag>_*:
-#   _bench_ae_bs256.json            the un-profiled bench line (BASELINE.json configs[1])
+# Produces under $OUT_DIR/<tag>_* (default profile_out/):
+#   _bench_ae_bs256.json            the un-profiled bench line (BASELINE.json configs[1]); bench.py --full wherever a line needs the
+#                                   objects beside the headline (roofline, north_star, vae, cpu_baseline, strong, allreduce)
 #   _bench_{vae,aeif}_bs256.json    configs[2] and configs[3]'s per-GPU workload, same command line otherwise
 #   _bench_ae_bs32.json             the reference's default minibatch size
 #   _bench_ae_bs256_kernel_stats.csv / _profiled.json   rocprofv3 --kernel-trace --stats of the same command
@@ -15,15 +16,19 @@
 # Copy the files you want judged into profiles/.
 tag=${1:-rXX}
 export TMPDIR=/tmp
-mkdir -p gpurun_out
+out=${OUT_DIR:-profile_out}
+export OUT_DIR=$out  # (tools/pmc_instmix.sh writes there too)
+mkdir -p $out
 if [ "$2" != "pmc" ]; then  # (second argument "pmc": only the PMC passes below — a source change that does not warrant the whole set)
-python bench.py --steps 100 --warmup 10 > gpurun_out/${tag}_bench_ae_bs256.json 2> gpurun_out/${tag}_bench.err
-python bench.py --steps 60 --warmup 10 --no-cpu-baseline --losses vae > gpurun_out/${tag}_bench_vae_bs256.json 2>> gpurun_out/${tag}_bench.err
-python bench.py --steps 60 --warmup 10 --no-cpu-baseline --losses autoencoder inverse forward > gpurun_out/${tag}_bench_aeif_bs256.json 2>> gpurun_out/${tag}_bench.err
-python bench.py --steps 150 --warmup 10 --no-cpu-baseline --no-kernel-timers --batch-size 32 > gpurun_out/${tag}_bench_ae_bs32.json 2>> gpurun_out/${tag}_bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$tag -o p -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-vae-leg \
-    > gpurun_out/${tag}_bench_ae_bs256_profiled.json 2> /dev/null
-cp "$(find /tmp/prof_$tag -name '*kernel_stats.csv' | head -1)" gpurun_out/${tag}_bench_ae_bs256_kernel_stats.csv
+python bench.py --full --steps 100 --warmup 10 > $out/${tag}_bench_ae_bs256.json 2> $out/${tag}_bench.err
+python bench.py --full --steps 60 --warmup 10 --no-cpu-baseline --losses vae > $out/${tag}_bench_vae_bs256.json 2>> $out/${tag}_bench.err
+python bench.py --full --steps 60 --warmup 10 --no-cpu-baseline --losses autoencoder inverse forward > $out/${tag}_bench_aeif_bs256.json \
+    2>> $out/${tag}_bench.err
+python bench.py --full --steps 150 --warmup 10 --no-cpu-baseline --no-kernel-timers --batch-size 32 > $out/${tag}_bench_ae_bs32.json \
+    2>> $out/${tag}_bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$tag -o p -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-vae-leg \
+    > $out/${tag}_bench_ae_bs256_profiled.json 2> /dev/null
+cp "$(find /tmp/prof_$tag -name '*kernel_stats.csv' | head -1)" $out/${tag}_bench_ae_bs256_kernel_stats.csv
 fi
 for ctr in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d /tmp/pmc_${tag}_$ctr -o p -- python bench.py --steps 3 --warmup 2 \
@@ -31,9 +36,9 @@ for ctr in FETCH_SIZE WRITE_SIZE; do
 done
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_LDS_BANK_CONFLICT --kernel-trace --output-format csv -d /tmp/pmc_${tag}_MFMA -o p -- \
     python bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-kernel-timers --no-vae-leg --allow-short > /dev/null 2>&1
-python - "$tag" <<'PY'
+python - "$tag" "$out" <<'PY'
 import csv, glob, json, sys, collections
-tag = sys.argv[1]
+tag, out_dir = sys.argv[1], sys.argv[2]
 sys.path.insert(0, ".")
 import bench  # csrc_sha16(): the kernel-source fingerprint bench.py compares against (roofline.stale)
 SHA = bench.csrc_sha16()
@@ -67,7 +72,7 @@ for name, c in per.items():
     wr = 1024.0 * sum(c["WRITE_SIZE"]) / len(c["WRITE_SIZE"])
     out["kernels"][short(name)] = {"launches": len(c["FETCH_SIZE"]), "read_bytes_per_launch": round(rd),
                                    "write_bytes_per_launch": round(wr), "hbm_bytes_per_launch": round(rd + wr)}
-json.dump(out, open("gpurun_out/%s_pmc_traffic.json" % tag, "w"), indent=1, sort_keys=True)
+json.dump(out, open("%s/%s_pmc_traffic.json" % (out_dir, tag), "w"), indent=1, sort_keys=True)
 
 # matrix-pipe occupancy: SQ_VALU_MFMA_BUSY_CYCLES counts cycles summed over the 1024 SIMDs, GRBM_GUI_ACTIVE the active cycles
 # summed over the 8 XCDs -> busy fraction = BUSY / (1024 * GUI / 8); clock = GUI / 8 / kernel duration
@@ -94,28 +99,29 @@ for name, a in acc.items():
                            "clock_ghz": round(gui / a["ns"], 3),
                            "mfma_busy_frac": round(a["SQ_VALU_MFMA_BUSY_CYCLES"] / (1024.0 * gui), 4),
                            "lds_bank_conflict_cycles_per_launch": round(a["SQ_LDS_BANK_CONFLICT"] / a["launches"])}
-json.dump(mf, open("gpurun_out/%s_pmc_mfma.json" % tag, "w"), indent=1, sort_keys=True)
+json.dump(mf, open("%s/%s_pmc_mfma.json" % (out_dir, tag), "w"), indent=1, sort_keys=True)
 PY
 # instruction mix per MFMA kernel and the split of its wave cycles (two more PMC passes) -> <tag>_instmix.txt
 bash tools/pmc_instmix.sh $tag -- python bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-kernel-timers --no-vae-leg --allow-short > /dev/null 2>&1
-[ -f gpurun_out/instmix_${tag}.txt ] && mv gpurun_out/instmix_${tag}.txt gpurun_out/${tag}_instmix.txt
+[ -f $out/instmix_${tag}.txt ] && mv $out/instmix_${tag}.txt $out/${tag}_instmix.txt
 if [ "$2" != "pmc" ]; then
 # the other configurations of BASELINE.json and the input modes, same sources, same box
-python bench.py --no-cpu-baseline --no-kernel-timers --losses vae --channels 6 --batch-size 128 --steps 40 > gpurun_out/${tag}_bench_vae_c6_bs128.json 2>> gpurun_out/${tag}_bench.err
-python bench.py --no-cpu-baseline --no-kernel-timers --losses triplet --batch-size 128 --steps 10 > gpurun_out/${tag}_bench_triplet_bs128.json 2>> gpurun_out/${tag}_bench.err
-python bench.py --no-cpu-baseline --no-kernel-timers --u8-resident --steps 30 > gpurun_out/${tag}_bench_ae_bs256_u8.json 2>> gpurun_out/${tag}_bench.err
-python bench.py --no-cpu-baseline --no-kernel-timers --host-input --steps 30 > gpurun_out/${tag}_bench_ae_bs256_hostinput.json 2>> gpurun_out/${tag}_bench.err
+python bench.py --no-cpu-baseline --no-kernel-timers --losses vae --channels 6 --batch-size 128 --steps 40 > $out/${tag}_bench_vae_c6_bs128.json 2>> $out/${tag}_bench.err
+python bench.py --no-cpu-baseline --no-kernel-timers --losses triplet --batch-size 128 --steps 10 > $out/${tag}_bench_triplet_bs128.json 2>> $out/${tag}_bench.err
+python bench.py --no-cpu-baseline --no-kernel-timers --u8-resident --steps 30 > $out/${tag}_bench_ae_bs256_u8.json 2>> $out/${tag}_bench.err
+python bench.py --no-cpu-baseline --no-kernel-timers --host-input --steps 30 > $out/${tag}_bench_ae_bs256_hostinput.json 2>> $out/${tag}_bench.err
 # eight ranks: RCCL when the box has eight GPUs, else the gloo debug topology on the GPUs there are (a functional line, not a scaling number)
 ngpu=$(python -c "import torch; print(torch.cuda.device_count())")
 if [ "$ngpu" -ge 8 ]; then
-  python bench.py --gpus 8 --steps 20 --warmup 5 > gpurun_out/${tag}_bench_rccl8.json 2>> gpurun_out/${tag}_bench.err
+  python bench.py --full --gpus 8 --steps 20 --warmup 5 > $out/${tag}_bench_rccl8.json 2>> $out/${tag}_bench.err
 else
-  SRLZ_DIST_BACKEND=gloo python bench.py --gpus 8 --batch-size 32 --steps 20 --warmup 3 --no-vae-leg > gpurun_out/${tag}_bench_gloo8.json 2>> gpurun_out/${tag}_bench.err
+  SRLZ_DIST_BACKEND=gloo python bench.py --full --gpus 8 --batch-size 32 --steps 20 --warmup 3 --no-vae-leg > $out/${tag}_bench_gloo8.json \
+      2>> $out/${tag}_bench.err
 fi
-python - "$tag" <<'PY'
+python - "$tag" "$out" <<'PY'
 import json, glob, sys
-tag = sys.argv[1]
-for f in sorted(glob.glob("gpurun_out/%s_bench_*.json" % tag)):
+tag, out_dir = sys.argv[1], sys.argv[2]
+for f in sorted(glob.glob("%s/%s_bench_*.json" % (out_dir, tag))):
     try:
         d = json.loads([l for l in open(f) if l.startswith("{")][-1])
         r = d.get("roofline", {})
@@ -125,4 +131,4 @@ for f in sorted(glob.glob("gpurun_out/%s_bench_*.json" % tag)):
         print(f, "unreadable", e)
 PY
 fi
-ls gpurun_out/${tag}_pmc_*.json gpurun_out/${tag}_instmix.txt
+ls $out/${tag}_pmc_*.json $out/${tag}_instmix.txt
