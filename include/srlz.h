@@ -606,6 +606,34 @@ int srlz_param_norms_grad(const float* const* ptrs, float* const* gptrs, const l
 int srlz_fold_grads(float* grad, float* stages, long long n, int nstage, srlz_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The reward-prior and episode-prior losses (csrc/priors.hip).  fp32 tensors, row-major; every reduction in a fixed order, no
+ * float atomics.
+ * ------------------------------------------------------------------------------------------------------------ */
+/* rewardPriorLoss losses/losses.py:290-304 with correlationMatrix losses/utils.py:120-134 (call: models/learner.py:470-474):
+ * out[0] = 1 - mean_j |clamp(corr[S, j], -1, 1)| of X = cat([states, rewards], 1)^T, states [B, S], rewards [B] (raw float
+ * rewards), B >= 2.  fwd leaves the reward statistics and per column (mean, inv stddev, corr, cov) in ws
+ * (srlz_reward_prior_workspace(S) bytes); bwd reads them: dstates [B, S] = g[0] * d out / d states. */
+size_t srlz_reward_prior_workspace(int S);
+int srlz_reward_prior_fwd(const float* states, const float* rewards, int B, int S, float* out, double* ws, size_t ws_bytes,
+                          srlz_stream_t stream);
+int srlz_reward_prior_bwd(const float* states, const float* rewards, const double* ws, size_t ws_bytes, const float* g, int B, int S,
+                          float* dstates, srlz_stream_t stream);
+/* episodePriorLoss losses/losses.py:307-359 with Discriminator / ReverseLayerF models/priors.py:129-175 (learner.py:476-479):
+ * out[0] = BCELoss(sum)(Discriminator(cat(s_i, s_{others[i]})), same_i), states [B, S], others int32 [B] in [0, B), same [B]
+ * (0 / 1), w1 [64, 2S], b1 [64], w2 [64, 64], b2 [64], w3 [1, 64], b3 [1].  An index outside [0, B) is never read through: it pairs
+ * its row with itself, consistently in fwd and bwd (srlz.ops.EpisodePriorFn rejects such indices when it is handed host indices).  fwd keeps the hidden activations and p in ws
+ * (srlz_episode_prior_workspace(B, S) bytes); ticket: one device int, zero before the first call, left zero by every call (the
+ * workgroup that finishes last adds the row terms).  bwd (two launches): dstates = -(d loss / d states) (the reversed gradient,
+ * lambda = 1) and the six parameter gradients (overwritten), all for upstream g[0]. */
+size_t srlz_episode_prior_workspace(int B, int S);
+int srlz_episode_prior_fwd(const float* states, const int* others, const float* same, int B, int S, const float* w1, const float* b1,
+                           const float* w2, const float* b2, const float* w3, const float* b3, float* out, void* ws, size_t ws_bytes,
+                           unsigned* ticket, srlz_stream_t stream);
+int srlz_episode_prior_bwd(const float* states, const int* others, const float* same, const float* g, int B, int S, const float* w1,
+                           const float* w2, const float* w3, void* ws, size_t ws_bytes, float* dstates, float* dw1, float* db1,
+                           float* dw2, float* db2, float* dw3, float* db3, srlz_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Adam over one flat parameter buffer — th.optim.Adam(params, lr) models/learner.py:199,495 (torch defaults).
  * step is 1-based; grad_scale multiplies g first (1/world_size after the RCCL sum).  The hyper-parameters are doubles, as
  * torch holds them: lr / (1 - beta1^step), sqrt(1 - beta2^step) and (1 - beta) are evaluated in double and rounded once.

@@ -1,11 +1,12 @@
-"""LossManager and the hot-path losses (reference losses/losses.py:19-59, 102-170, 172-214, 239-256).
+"""LossManager and the hot-path losses (reference losses/losses.py:19-59, 102-170, 172-214, 239-256, 290-359, 360-376).
 
 Same function names, argument order and return values as the reference; the reductions and their gradients run as
-fused HIP kernels (srlz/ops.py).  Losses of other SRL methods (priors, episode/reward priors) are outside the
-hot path and not provided.
+fused HIP kernels (srlz/ops.py).  The reward prior and the episode prior run on csrc/priors.hip; the robotic-priors loss
+(`priors`, with its pair mining) and the mutual-information loss are outside the hot path and not provided.
 """
 from __future__ import print_function, division, absolute_import
 
+import numpy as np
 import torch as th
 
 from srlz import ops
@@ -156,3 +157,59 @@ def tripletLoss(states, p_states, n_states, weight, loss_manager, alpha=0.2):
     tcn_triplet_loss = ops.TripletLossFn.apply(states, p_states, n_states, alpha)
     loss_manager.addToLosses('triplet_loss', weight, tcn_triplet_loss)
     return _returned(tcn_triplet_loss, weight, loss_manager)
+
+
+def rewardPriorLoss(states, rewards_st, weight, loss_manager):
+    """1 - mean over the last row of |corr(cat([states, rewards], 1)^T)|: states correlated with the reward (reference
+    losses.py:290-304).  rewards_st: the minibatch's raw rewards as float32, [B] or [B, 1]."""
+    reward_prior_loss = ops.RewardPriorFn.apply(states, rewards_st)
+    loss_manager.addToLosses('reward_prior', weight, reward_prior_loss)
+    return _returned(reward_prior_loss, weight, loss_manager)
+
+
+def sampleEpisodeOthers(episodes, balanced_sampling):
+    """The partner row of every row of a minibatch for the episode prior, drawn from numpy's global RNG with the same calls, in the
+    same order, as the reference's episodePriorLoss (losses.py:335-347), so that a seeded run draws the same partners:
+      * uniform: one permutation of the rows;
+      * balanced: per row, rand() > 0.5 picks uniformly (np.random.choice) among the rows of OTHER episodes, otherwise among the rows
+        of its own episode (itself included).  No other-episode row raises ValueError, as np.random.choice([]) does there.
+    :param episodes: episode id of every row of the minibatch
+    :return: (others int64 [B], same float32 [B]: 1 where the partner lies in the row's episode)"""
+    episodes = np.asarray(episodes)
+    n = len(episodes)
+    if balanced_sampling:
+        others = np.arange(n)
+        for i in range(n):
+            mates = episodes == episodes[i]
+            pool = np.flatnonzero(~mates) if np.random.rand() > 0.5 else np.flatnonzero(mates)
+            others[i] = np.random.choice(pool)
+    else:
+        others = np.random.permutation(n)
+    return others, (episodes == episodes[others]).astype(np.float32)
+
+
+def episodeInputs(others, same, device):
+    """(others, same) of sampleEpisodeOthers as the device tensors ops.EpisodePriorFn takes: int32 indices (checked here, on the host,
+    to lie inside the minibatch) and float32 targets, both copied without blocking the host."""
+    others = np.asarray(others)
+    if others.size and (others.min() < 0 or others.max() >= len(others)):
+        raise ValueError("episode prior: partner indices must lie in [0, %d)" % len(others))
+    o = th.from_numpy(others.astype(np.int32))
+    y = th.from_numpy(np.asarray(same, dtype=np.float32))
+    if device.type == "cuda":
+        o, y = o.pin_memory(), y.pin_memory()
+    return o.to(device, non_blocking=True), y.to(device, non_blocking=True)
+
+
+def episodePriorLoss(minibatch_idx, minibatch_episodes, states, discriminator, balanced_sampling, weight, loss_manager,
+                     others=None):
+    """Episode prior (reference losses.py:307-359): a discriminator learns whether two states come from the same episode, and the
+    states receive its reversed gradient (ReverseLayerF, lambda = 1), so that they learn to fool it.  BCELoss(reduction='sum').
+    others: (others int32 [B], same float32 [B]) device tensors drawn by the caller (the trainer draws them per step with
+    sampleEpisodeOthers and uploads them with the minibatch); None: drawn here from minibatch_episodes[minibatch_idx]."""
+    if others is None:
+        o, y = sampleEpisodeOthers(np.array(minibatch_episodes[minibatch_idx]), balanced_sampling)
+        others = episodeInputs(o, y, states.device)
+    episode_loss = ops.EpisodePriorFn.apply(states, others[0], others[1], *discriminator.params())
+    loss_manager.addToLosses('episode_prior', weight, episode_loss)
+    return _returned(episode_loss, weight, loss_manager)

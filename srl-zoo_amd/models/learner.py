@@ -21,12 +21,14 @@ import numpy as np
 import torch as th
 
 from losses.losses import LossManager, autoEncoderLoss, forwardModelLoss, inverseModelLoss, kullbackLeiblerLoss, \
-    generationLoss, rewardModelLoss, l1Loss, l2Loss, perceptualSimilarityLoss, tripletLoss
+    generationLoss, rewardModelLoss, l1Loss, l2Loss, perceptualSimilarityLoss, tripletLoss, rewardPriorLoss, episodePriorLoss, \
+    sampleEpisodeOthers, episodeInputs
 from pipeline import NAN_ERROR
 from preprocessing.data_loader import DataLoader
 from utils import printRed, detachToNumpy, printYellow
 from srlz import optim
 from .modules import SRLModules, SRLModulesSplit
+from .priors import Discriminator
 
 MAX_BATCH_SIZE_GPU = 256  # minibatch size used when predicting states
 EPOCH_FLAG = 1            # print every epoch
@@ -44,7 +46,8 @@ RAW_UINT8_INPUT = True
 # (preprocessing/resident.py); False restores the reference's re-decoding of every epoch (A/B, tests)
 RESIDENT_FRAMES = True
 
-SUPPORTED_LOSSES = {"autoencoder", "vae", "dae", "forward", "inverse", "reward", "perceptual", "random", "triplet"}
+SUPPORTED_LOSSES = {"autoencoder", "vae", "dae", "forward", "inverse", "reward", "perceptual", "random", "triplet", "reward-prior",
+                    "episode-prior"}
 
 
 def n_epochs_planned(losses):
@@ -254,6 +257,11 @@ class SRL4robotics(BaseLearner):
         self.use_vae = "vae" in losses
         self.use_dae = "dae" in losses
         self.use_triplets = "triplet" in losses
+        self.reward_prior = "reward-prior" in losses
+        self.episode_prior = "episode-prior" in losses
+        if self.use_triplets and (self.reward_prior or self.episode_prior):
+            raise NotImplementedError("'reward-prior' / 'episode-prior' cannot be combined with 'triplet' in this build (the triplet "
+                                      "step's states come from the frozen EmbeddingNet trunk)")
         if self.use_triplets and (self.use_vae or self.use_autoencoder or self.use_dae):
             # the reference itself crashes on `vae triplet` (mu / logvar are never bound, learner.py:383-414 vs 457-459) and
             # silently drops the auto-encoder for the EmbeddingNet: there is no behaviour to reproduce
@@ -276,6 +284,9 @@ class SRL4robotics(BaseLearner):
         _requireGpu(cuda)
         self.cuda = cuda
         self.device = th.device("cuda", th.cuda.current_device())
+        # the episode prior's discriminator, built right after the model as in the reference (learner.py:189-190: same torch RNG
+        # order); its parameters join the optimizer, not the model's state_dict (srl_model.pth) nor the regularisers
+        self.discriminator = Discriminator(2 * self.state_dim).to(self.device) if self.episode_prior else None
         self.model = self.model.to(self.device)
         self.rank, self.world_size = optim.world()
 
@@ -290,8 +301,9 @@ class SRL4robotics(BaseLearner):
         from srlz import ops as _ops
         _ops.norm_lut(self.device)  # built eagerly: its first use must not fall inside a stream capture or on a side stream
 
-        # one flat parameter / gradient buffer + fused Adam (torch.optim.Adam defaults)
-        self.flat_params = optim.FlatParams(self.model)
+        # one flat parameter / gradient buffer + fused Adam (torch.optim.Adam defaults); the discriminator's parameters follow the
+        # model's in the same buffer (learner.py:194-199: one optimizer over both lists)
+        self.flat_params = optim.FlatParams(*([self.model] + ([self.discriminator] if self.discriminator is not None else [])))
         self.optimizer = optim.FusedAdam(self.flat_params, lr=learning_rate)
         self.log_folder = log_folder
         self.model_type = model_type
@@ -397,20 +409,23 @@ class SRL4robotics(BaseLearner):
         return self.model(x), self.model(next_x)
 
     def trainStep(self, obs, next_obs, actions_st, loss_manager, validation_mode=False, noisy_obs=None,
-                  next_noisy_obs=None, rewards_st=None):
+                  next_noisy_obs=None, rewards_st=None, reward_prior_st=None, episode_others=None, episode_same=None):
         """The minibatch-loop body of the reference (models/learner.py:362-497) on device tensors.
 
         Runs forward, losses, backward (also on validation minibatches, as the reference does), the gradient
         all-reduce and the Adam step.  Returns the total loss as a 0-dim device tensor; per-loss tensors stay in
         `loss_manager`.  With hipGraph mode on (SRLZ_GRAPH, see _graphStep) the same body is replayed from a captured
         graph: one launch per step instead of ~300.
+        reward_prior_st: the minibatch's raw rewards, float32 [B] (reward prior); episode_others / episode_same: the episode prior's
+        partner rows (int32 [B]) and targets (float32 [B]) of this step (losses.sampleEpisodeOthers / episodeInputs).
         """
         if self._use_graph and self.world_size == 1:
             return self._graphStep(loss_manager, validation_mode, dict(obs=obs, next_obs=next_obs, actions_st=actions_st,
                                                                        noisy_obs=noisy_obs, next_noisy_obs=next_noisy_obs,
-                                                                       rewards_st=rewards_st))
+                                                                       rewards_st=rewards_st, reward_prior_st=reward_prior_st,
+                                                                       episode_others=episode_others, episode_same=episode_same))
         return self._eagerStep(obs, next_obs, actions_st, loss_manager, validation_mode, noisy_obs, next_noisy_obs,
-                               rewards_st)
+                               rewards_st, reward_prior_st, episode_others, episode_same)
 
     # -- hipGraph mode ----------------------------------------------------------------------------------------------
     # The step body can be captured ONCE per variant (training / validation) into a HIP graph
@@ -469,7 +484,7 @@ class SRL4robotics(BaseLearner):
         return entry["loss"]
 
     def _eagerStep(self, obs, next_obs, actions_st, loss_manager, validation_mode=False, noisy_obs=None,
-                   next_noisy_obs=None, rewards_st=None):
+                   next_noisy_obs=None, rewards_st=None, reward_prior_st=None, episode_others=None, episode_same=None):
         if validation_mode:
             self.model.eval()
         else:
@@ -520,8 +535,11 @@ class SRL4robotics(BaseLearner):
         # the states feed several heads (and, as next_states, the forward loss): explicit fan-outs, one alias per consumer, so that the
         # gradients coming back are summed by one launch each (ops.FanOutFn) instead of one accumulation kernel per extra consumer
         n_heads = int(self.use_forward_loss) + int(self.use_inverse_loss) + int(self.use_reward_loss)
-        states_fan, next_states_fan = ops.Fan(states, n_heads + int(self.use_triplets)), ops.Fan(next_states, n_heads)
-        # same order as the reference's loop body (learner.py:420-449): regularisers, forward, inverse, reward, AE, VAE
+        n_priors = int(self.reward_prior) + int(self.episode_prior)
+        states_fan = ops.Fan(states, n_heads + int(self.use_triplets) + n_priors)
+        next_states_fan = ops.Fan(next_states, n_heads)
+        # same order as the reference's loop body (learner.py:420-482): regularisers, forward, inverse, reward, AE, VAE, reward prior,
+        # episode prior, triplet
         # (the terms are read from the LossManager below; the loss functions' own `weight * loss` return values would be one launch
         # per term for nobody)
         loss_manager.collect_only = True
@@ -555,6 +573,15 @@ class SRL4robotics(BaseLearner):
             else:
                 generationLoss(decoded_obs, decoded_next_obs, ops.frames_as_float(obs), ops.frames_as_float(next_obs),
                                weight=w['vae'], loss_manager=loss_manager)
+        if self.reward_prior:
+            if reward_prior_st is None:
+                raise ValueError("the reward prior needs the minibatch's rewards (trainStep(..., reward_prior_st=...))")
+            rewardPriorLoss(states_fan.take(), reward_prior_st, weight=w['reward-prior'], loss_manager=loss_manager)
+        if self.episode_prior:
+            if episode_others is None or episode_same is None:
+                raise ValueError("the episode prior needs the step's partner rows (trainStep(..., episode_others=..., episode_same=...))")
+            episodePriorLoss(None, None, states_fan.take(), self.discriminator, BALANCED_SAMPLING, weight=w['episode-prior'],
+                             loss_manager=loss_manager, others=(episode_others, episode_same))
 
         if self.use_triplets:
             tripletLoss(states_fan.take(), positive_states, negative_states, weight=w['triplet'], loss_manager=loss_manager, alpha=0.2)
@@ -616,6 +643,12 @@ class SRL4robotics(BaseLearner):
                 "Not enough minibatches for {} GPUs: every rank needs at least one training and one validation " \
                 "minibatch per epoch ({} / {} available)".format(self.world_size, len(minibatchlist) - n_val_batches,
                                                                 n_val_batches)
+
+        minibatch_episodes = None
+        if self.episode_prior:
+            # episode id of every sample (learner.py:328-330), per minibatch
+            episode_of = np.cumsum(episode_starts)
+            minibatch_episodes = [episode_of[mb] for mb in minibatchlist]
 
         n_actions = int(np.max(actions) + 1)
         # the cross-entropy / one-hot kernels index by target: reject what nn.CrossEntropyLoss / scatter_ would reject
@@ -740,8 +773,16 @@ class SRL4robotics(BaseLearner):
                     rewards_st[rewards_st == -1] = 0  # removing negative reward (reference learner.py:439-441)
                     rewards_st = th.from_numpy(rewards_st).to(self.device).long()
 
+                reward_prior_st = episode_others = episode_same = None
+                if self.reward_prior:  # the raw rewards as float32 (learner.py:470-474: no -1 -> 0 mapping here)
+                    reward_prior_st = th.from_numpy(np.asarray(rewards[minibatchlist[minibatch_idx]], dtype=np.float32))
+                    reward_prior_st = reward_prior_st.to(self.device)
+                if self.episode_prior:  # the step's draw from the global numpy RNG, training and validation alike (losses.py:335-347)
+                    episode_others, episode_same = episodeInputs(
+                        *sampleEpisodeOthers(minibatch_episodes[minibatch_idx], BALANCED_SAMPLING), device=self.device)
+
                 loss = self.trainStep(obs, next_obs, actions_st, loss_manager, validation_mode, noisy_obs,
-                                      next_noisy_obs, rewards_st)
+                                      next_noisy_obs, rewards_st, reward_prior_st, episode_others, episode_same)
                 feed.advance()  # next minibatch's H2D copy overlaps this step (issued before the host waits below)
                 if fill is not None:
                     fill.drain()  # whatever chunks of the own slice are decoded by now

@@ -1,7 +1,8 @@
 """The plain dense encoders of the reference's models/priors.py (module name kept for the plugin surface): SRLDenseNetwork
 (priors.py:71-102) and SRLLinear (priors.py:105-125), the `--model-type mlp | linear` models of the losses that need no decoder
-(inverse / forward / reward).  Their nn.Linear(input_dim, .) runs on csrc/dense.hip.  The priors loss family itself stays outside
-this build."""
+(inverse / forward / reward).  Their nn.Linear(input_dim, .) runs on csrc/dense.hip.  Also the episode prior's Discriminator and
+ReverseLayerF (priors.py:129-175): the discriminator holds the parameters, its forward and backward run inside ops.EpisodePriorFn
+(csrc/priors.hip).  The robotic-priors loss (`priors`) stays outside this build."""
 from __future__ import print_function, division, absolute_import
 
 import torch as th
@@ -67,3 +68,32 @@ class SRLLinear(BaseModelSRL):
 
     def forward(self, x):
         return hotpath.dense_in(self.fc, x)
+
+
+ReverseLayerF = ops.ReverseLayerF  # (reference priors.py:129-152: identity forward, -lambda * gradient backward)
+
+
+class Discriminator(nn.Module):
+    """Linear(input_dim, 64)-ReLU-Linear(64, 64)-ReLU-Linear(64, 1)-Sigmoid (reference priors.py:155-175), same keys (net.0 / net.2 /
+    net.4) and the same initialisation order.  Parameters only: episodePriorLoss evaluates it through ops.EpisodePriorFn, which
+    gathers its input pairs, runs the three layers and the BCE in one launch.
+    :input_dim: (int) input_dim = 2 * state_dim"""
+
+    def __init__(self, input_dim):
+        super(Discriminator, self).__init__()
+        self.net = nn.Sequential(
+            nn.Linear(input_dim, 64),
+            nn.ReLU(inplace=True),
+            nn.Linear(64, 64),
+            nn.ReLU(inplace=True),
+            nn.Linear(64, 1),
+            nn.Sigmoid()
+        )
+
+    def params(self):
+        """(w1, b1, w2, b2, w3, b3), the order ops.EpisodePriorFn takes them in."""
+        return (self.net[0].weight, self.net[0].bias, self.net[2].weight, self.net[2].bias, self.net[4].weight, self.net[4].bias)
+
+    def forward(self, x):
+        raise NotImplementedError("Discriminator runs inside the episode-prior loss (ops.EpisodePriorFn, csrc/priors.hip); "
+                                  "call losses.losses.episodePriorLoss")

@@ -185,6 +185,12 @@ _PROTOS = {
     "srlz_reparam_fwd": (c_int, [P, P, P, P, c_longlong, P]),
     "srlz_reparam_bwd": (c_int, [P, P, P, P, P, c_longlong, P]),
     "srlz_cross_entropy": (c_int, [P, P, c_int, c_int, P, P, P]),
+    "srlz_reward_prior_workspace": (c_size_t, [c_int]),
+    "srlz_reward_prior_fwd": (c_int, [P, P, c_int, c_int, P, P, c_size_t, P]),
+    "srlz_reward_prior_bwd": (c_int, [P, P, P, c_size_t, P, c_int, c_int, P, P]),
+    "srlz_episode_prior_workspace": (c_size_t, [c_int, c_int]),
+    "srlz_episode_prior_fwd": (c_int, [P, P, P, c_int, c_int, P, P, P, P, P, P, P, P, c_size_t, P, P]),
+    "srlz_episode_prior_bwd": (c_int, [P, P, P, P, c_int, c_int, P, P, P, P, c_size_t, P, P, P, P, P, P, P, P]),
     "srlz_concat_onehot": (c_int, [P, P, P, c_int, c_int, c_int, P]),
     "srlz_normalize_u8": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
     "srlz_mask_columns": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),

@@ -1596,6 +1596,121 @@ class TripletLossFn(Function):
         return ds, dp, dn, None
 
 
+class RewardPriorFn(Function):
+    """1 - mean_j |clamp(corr[S, j], -1, 1)| of the correlation matrix of cat([states, rewards], 1)^T — rewardPriorLoss with
+    correlationMatrix, reference losses/losses.py:290-304, losses/utils.py:120-134.  `rewards`: the raw float rewards [B] or [B, 1].
+    One launch forward (fp64 column statistics, kept for the backward), one launch backward."""
+
+    @staticmethod
+    def forward(ctx, states, rewards):
+        states, rewards = _check(states, "reward-prior states"), _check(rewards, "reward-prior rewards")
+        if states.dim() != 2 or rewards.numel() != states.shape[0]:
+            raise C.SrlzError("reward prior: states [B, S] and rewards [B] expected, got %s and %s"
+                              % (tuple(states.shape), tuple(rewards.shape)))
+        b, s = states.shape
+        if b < 2:
+            raise C.SrlzError("reward prior: the correlation needs at least 2 rows (got %d)" % b)
+        nbytes = C.reward_prior_workspace(s)
+        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=states.device)
+        out = torch.empty((), dtype=torch.float32, device=states.device)
+        C.reward_prior_fwd(ptr(states), ptr(rewards), b, s, ptr(out), ptr(ws), nbytes, stream())
+        ctx.save_for_backward(states, rewards, ws)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        states, rewards, ws = ctx.saved_tensors
+        b, s = states.shape
+        ds = torch.empty_like(states)
+        C.reward_prior_bwd(ptr(states), ptr(rewards), ptr(ws), ws.numel() * 8, ptr(_check(g, "loss grad")), b, s, ptr(ds), stream())
+        return ds, None
+
+
+_EP_TICKETS = {}
+
+
+def _episode_ticket(device):
+    """The episode-prior forward's completion counter (one int per device, zero between launches)."""
+    t = _EP_TICKETS.get(device.index)
+    if t is None:
+        t = torch.zeros(1, dtype=torch.int32, device=device)
+        _EP_TICKETS[device.index] = t
+    return t
+
+
+class EpisodePriorFn(Function):
+    """BCELoss(reduction='sum')(Discriminator(cat(s, s[others])), same) with the gradient into the states reversed — episodePriorLoss
+    with ReverseLayerF (lambda = 1) and Discriminator, reference losses/losses.py:307-359, models/priors.py:129-175.
+    `others`: int32 [B] indices in [0, B) — a device tensor as losses.episodeInputs uploads it, or a host tensor / array, which is
+    range-checked here and uploaded (on the device an index outside the batch pairs its row with itself, include/srlz.h);
+    `same`: float32 [B] (1 where others[i] is in row i's episode);
+    `disc_params`: net.0.weight, net.0.bias, net.2.weight, net.2.bias, net.4.weight, net.4.bias.  One launch forward, two backward;
+    the six parameter gradients are written straight into the gradient bucket when the parameters live there."""
+
+    @staticmethod
+    def forward(ctx, states, others, same, w1, b1, w2, b2, w3, b3):
+        states, same = _check(states, "episode-prior states"), _check(same, "episode-prior targets")
+        if states.dim() != 2:
+            raise C.SrlzError("episode prior: states [B, S] expected, got %s" % (tuple(states.shape),))
+        b, s = states.shape
+        if not torch.is_tensor(others) or others.device.type == "cpu":
+            host = torch.as_tensor(others)
+            if host.dtype not in (torch.int32, torch.int64) or host.numel() != b or \
+                    (b and (int(host.min()) < 0 or int(host.max()) >= b)):
+                raise C.SrlzError("episode prior: partner indices must be %d integers in [0, %d)" % (b, b))
+            others = host.to(torch.int32).to(states.device)
+        if others.dtype != torch.int32 or others.device != states.device or others.numel() != b or same.numel() != b:
+            raise C.SrlzError("episode prior: others must be int32 [%d] and same float32 [%d] on the states' device" % (b, b))
+        shapes = ((64, 2 * s), (64,), (64, 64), (64,), (1, 64), (1,))
+        params = (w1, b1, w2, b2, w3, b3)
+        for p, shape in zip(params, shapes):
+            if tuple(p.shape) != shape:
+                raise C.SrlzError("episode prior: discriminator parameter of shape %s, expected %s" % (tuple(p.shape), shape))
+        ps = [_check(p, "discriminator parameter") for p in params]
+        others = others.contiguous()
+        nbytes = C.episode_prior_workspace(b, s)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=states.device)
+        out = torch.empty((), dtype=torch.float32, device=states.device)
+        C.episode_prior_fwd(ptr(states), ptr(others), ptr(same), b, s, *[ptr(p) for p in ps], ptr(out), ptr(ws), nbytes,
+                            ptr(_episode_ticket(states.device)), stream())
+        ctx.save_for_backward(states, others, same, ws, ps[0], ps[2], ps[4])
+        ctx.params = params
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        states, others, same, ws, w1, w2, w3 = ctx.saved_tensors
+        b, s = states.shape
+        ds = torch.empty_like(states)
+        grads = [_gbuf(p) for p in ctx.params]
+        C.episode_prior_bwd(ptr(states), ptr(others), ptr(same), ptr(_check(g, "loss grad")), b, s, ptr(w1), ptr(w2), ptr(w3), ptr(ws),
+                            ws.numel(), ptr(ds), *[ptr(x) for x in grads], stream())
+        return (ds, None, None) + tuple(_give(p, x) for p, x in zip(ctx.params, grads))
+
+
+_ONES = {}
+
+
+class ReverseLayerF(Function):
+    """Identity forward, -lambda * gradient backward (reference models/priors.py:129-152).  The episode prior applies the reversal
+    inside EpisodePriorFn's backward; this stand-alone form is kept for callers of the reference's name."""
+
+    @staticmethod
+    def forward(ctx, x, lambda_):
+        ctx.lambda_ = float(lambda_)
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = _check(dy, "reversed gradient")
+        one = _ONES.get(dy.device.index)
+        if one is None:
+            one = _ONES[dy.device.index] = torch.ones(1, dtype=torch.float32, device=dy.device)
+        dx = torch.empty_like(dy)
+        C.scale_by_scalar(ptr(dy), ptr(one), 1.0, -ctx.lambda_, ptr(dx), dy.numel(), stream())
+        return dx, None
+
+
 class ConcatOneHotFn(Function):
     """cat([s, onehot(a)], 1) — forwardModel's input, forward_inverse.py:30 + models/models.py:229-237."""
 

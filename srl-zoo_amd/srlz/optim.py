@@ -12,13 +12,15 @@ from . import ops
 
 
 class FlatParams(object):
-    """Re-homes every parameter of `module` into one contiguous fp32 buffer (+ a matching gradient buffer)."""
+    """Re-homes every parameter of `modules` into one contiguous fp32 buffer (+ a matching gradient buffer), module after module
+    in the order given (the trainer passes the model, then the episode prior's discriminator: one bucket, one all-reduce and one
+    fused Adam for both, as the reference's single optimizer over both parameter lists, learner.py:194-199)."""
 
     ALIGN = 4  # floats (16 bytes)
     TAIL = 16  # loss scalars riding behind the gradients (slot 0 = total loss: a NaN / inf on ANY rank shows on EVERY rank)
 
-    def __init__(self, module):
-        params = [p for p in module.parameters() if p.requires_grad]
+    def __init__(self, *modules):
+        params = [p for module in modules for p in module.parameters() if p.requires_grad]
         if not params:
             raise ValueError("module has no trainable parameter")
         device = params[0].device

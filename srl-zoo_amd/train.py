@@ -3,9 +3,10 @@ driving the MI355X-native SRL4robotics.  Multi-GPU: launch one process per GPU w
 ``python -m torch.distributed.run --nproc-per-node N train.py ...`` (RANK / LOCAL_RANK / WORLD_SIZE are read from the
 environment; backend "nccl" is RCCL on ROCm).
 
---model-type custom_cnn, mlp and linear run (mlp / linear without a split representation, perceptual or triplet).
-Out of scope of this build (rejected with a clear message): --model-type resnet, the losses of other SRL methods (priors,
-episode-prior, reward-prior), plots.
+--model-type custom_cnn, mlp and linear run (mlp / linear without a split representation, perceptual or triplet), as do the
+reward-prior and episode-prior losses (--balanced-sampling selects the episode prior's balanced partner draw).
+Out of scope of this build (rejected with a clear message): --model-type resnet, the robotic-priors loss (priors), reward-prior /
+episode-prior combined with triplet, plots.
 """
 from __future__ import print_function, division, absolute_import
 
@@ -46,7 +47,7 @@ _CLI = [
     (("--data-folder",), _STR, "", "dataset folder under data/ (required)"),
     (("--log-folder",), _STR, "", "output folder (default: logs/<dataset>/<timestamp>_<model>_ST_DIM<n>_<losses>)"),
     (("--multi-view",), _FLAG, False, "two stacked camera views (6 input channels)"),
-    (("--balanced-sampling",), _FLAG, False, "accepted for compatibility (episode prior only)"),
+    (("--balanced-sampling",), _FLAG, False, "episode prior: draw partners half from other episodes, half from the same one"),
     (("--beta",), _FLOAT, 1.0, "weight of the KL term (beta-VAE)"),
     (("--path-to-dae",), _STR, "", "srl_model.pth of a trained DAE (perceptual loss)"),
     (("--state-dim-dae",), _INT, 200, "state dimension of that DAE"),

@@ -98,12 +98,23 @@ def bn_digest(model, out, prefix="bn/"):
 
 def step_case(th, ref_pre, SRLModules, RL, losses, B, C=3, S=200, A=6, n_steps=1, lr=None,
               eps_seed=99, beta=1.0, inverse="linear", weights=None, split=None, l1_reg=0.0, l2_reg=0.0, val_steps=(),
-              model_type="custom_cnn"):
+              model_type="custom_cnn", balanced=False):
     """One (or several) loop bodies of models/learner.py:373-497 driven on the reference classes.
     `val_steps`: steps run as validation minibatches (learner.py:362-364,487-497: eval mode, forward + backward, no
-    optimizer step)."""
+    optimizer step).
+    reward-prior / episode-prior: the raw golden rewards as float32; the episode prior's Discriminator is built right after the model
+    (learner.py:189-190), its episodes are EPISODES[:B], np.random is seeded with 777 + step before the loss draws its partners
+    (`balanced`: BALANCED_SAMPLING), and the drawn partner rows are recorded (episode/others)."""
     model = build(th, ref_pre, SRLModules, [l for l in losses if l != "perceptual"] if split is None else losses, S=S, A=A,
                   C=C, inverse=inverse, split=split, model_type=model_type)
+    disc = None
+    if "episode-prior" in losses:
+        from models.priors import Discriminator  # the reference's
+        disc = Discriminator(2 * S)
+        disc_inputs = []
+        disc.register_forward_pre_hook(lambda _m, inp: disc_inputs.append(inp[0].detach().clone()))
+        episodes = np.array(EPISODES[:B])
+        drawn = []
     denoiser = None
     if "perceptual" in losses:  # the frozen, eval-mode DAE of learner.py:317-326 (seed 7 stands in for "pre-trained")
         denoiser = build(th, ref_pre, SRLModules, ["dae"], S=S, A=A, C=C, seed=7)
@@ -111,12 +122,15 @@ def step_case(th, ref_pre, SRLModules, RL, losses, B, C=3, S=200, A=6, n_steps=1
         for param in denoiser.parameters():
             param.requires_grad = False
     w = {"forward": 1.0, "inverse": 2.0, "reward": 1.0, "autoencoder": 1.0, "dae": 1.0, "vae": 0.5e-6, "perceptual": 1e-6}
+    if disc is not None or "reward-prior" in losses:
+        w.update({"reward-prior": 10, "episode-prior": 1.0})
     if weights:
         w.update(weights)
     out = {}
     opt = None
     if lr is not None:
-        opt = th.optim.Adam([p for p in model.parameters() if p.requires_grad], lr=lr)
+        opt = th.optim.Adam([p for p in model.parameters() if p.requires_grad] + ([p for p in disc.parameters()] if disc is not None
+                                                                                   else []), lr=lr)
     history = {}
     lm = RL.LossManager(model, None)
     trace = []
@@ -170,6 +184,14 @@ def step_case(th, ref_pre, SRLModules, RL, losses, B, C=3, S=200, A=6, n_steps=1
                 RL.perceptualSimilarityLoss(sd_real, sd_pred, nsd_real, nsd_pred, weight=w["perceptual"], loss_manager=lm)
             else:
                 RL.generationLoss(dec, next_dec, obs, next_obs, weight=w["vae"], loss_manager=lm)
+        if "reward-prior" in losses:
+            raw, _ = golden_rewards(B, seed=1234 + step)
+            RL.rewardPriorLoss(states, th.from_numpy(raw.astype(np.float32)).view(-1, 1), weight=w["reward-prior"], loss_manager=lm)
+        if disc is not None:
+            np.random.seed(777 + step)
+            RL.episodePriorLoss(0, [episodes], states, disc, balanced, weight=w["episode-prior"], loss_manager=lm)
+            pairs = disc_inputs[-1][:, S:]
+            drawn.append([int(np.flatnonzero((states.detach() == pairs[i]).all(1).numpy())[0]) for i in range(B)])
         loss = lm.computeTotalLoss()
         loss.backward()
         rec = {n: float(l.item()) for n, l in zip(lm.names, lm.losses)}
@@ -194,6 +216,8 @@ def step_case(th, ref_pre, SRLModules, RL, losses, B, C=3, S=200, A=6, n_steps=1
                     out["next_logvar/" + k] = v
             grads_digest(model, out)
             bn_digest(model, out)
+            if disc is not None:
+                grads_digest(disc, out, prefix="disc_grad/")
         if opt is not None and step not in val_steps:
             opt.step()
     if n_steps > 1 or opt is not None:
@@ -203,12 +227,62 @@ def step_case(th, ref_pre, SRLModules, RL, losses, B, C=3, S=200, A=6, n_steps=1
         sd = digest_state_dict(model.state_dict())
         out["final/names"], out["final/sums"], out["final/abss"] = sd["names"], sd["sums"], sd["abss"]
         bn_digest(model, out, prefix="final_bn/")
+        if disc is not None:
+            sd = digest_state_dict(disc.state_dict())
+            out["final_disc/names"], out["final_disc/sums"], out["final_disc/abss"] = sd["names"], sd["sums"], sd["abss"]
+    if disc is not None:
+        out["episode/ids"] = episodes
+        out["episode/others"] = np.array(drawn, dtype=np.int64)
     # eval-mode states on the (possibly updated) model: the "learned states" output (learner.py:67-88)
     model.eval()
     with th.no_grad():
         obs, _, _ = golden_inputs(B, C, A, seed=1234)
         st = model.getStates(th.from_numpy(obs))
     out["eval_states/full"] = st.double().numpy()
+    return out
+
+
+EPISODES = [0, 0, 1, 1, 1, 2, 3, 3]  # episode ids of the rows of a prior step case (B <= 8)
+
+
+def prior_kats(th):
+    """The reference's episode-prior partner draws (losses.py:335-347) for a few episode vectors, seeds and both sampling modes,
+    recovered from the rows its Discriminator receives; a single-episode minibatch under balanced sampling records the error; the
+    seeded Discriminator(2 S) parameters (priors.py:155-175)."""
+    import losses.losses as RL
+    from models.priors import Discriminator
+    out = {}
+    cases = [[0, 0, 1, 1], [0, 1, 1, 1, 2, 2, 3], [3, 3, 3, 5, 5, 7, 7, 7, 7, 8], list(range(6))]
+    for ci, eps in enumerate(cases):
+        eps = np.array(eps)
+        B = len(eps)
+        states = th.arange(B * 3, dtype=th.float32).view(B, 3)
+        seen = []
+
+        def disc(x):
+            seen.append(x.detach().clone())
+            return th.full((x.shape[0], 1), 0.5)
+        for balanced in (False, True):
+            for seed in (0, 1, 2):
+                np.random.seed(seed)
+                draws = []
+                for _ in range(3):  # three consecutive steps from one seed
+                    RL.episodePriorLoss(0, [eps], states, disc, balanced, 1.0, RL.LossManager(th.nn.Linear(1, 1), None))
+                    pairs = seen[-1][:, 3:]
+                    draws.append([int(np.flatnonzero((states == pairs[i]).all(1).numpy())[0]) for i in range(B)])
+                out["case%d/%s/seed%d" % (ci, "balanced" if balanced else "uniform", seed)] = np.array(draws, dtype=np.int64)
+        out["case%d/episodes" % ci] = eps
+    try:
+        np.random.seed(0)
+        RL.episodePriorLoss(0, [np.zeros(4, dtype=np.int64)], th.zeros(4, 3), lambda x: th.full((4, 1), 0.5), True, 1.0,
+                            RL.LossManager(th.nn.Linear(1, 1), None))
+        out["single_episode/error"] = np.array("none")
+    except Exception as e:
+        out["single_episode/error"] = np.array(type(e).__name__)
+    for S in (2, 200):
+        th.manual_seed(5)
+        sd = digest_state_dict(Discriminator(2 * S).state_dict())
+        out["disc_s%d/names" % S], out["disc_s%d/sums" % S], out["disc_s%d/abss" % S] = sd["names"], sd["sums"], sd["abss"]
     return out
 
 
@@ -351,7 +425,8 @@ def _install_cv2_shim():
     cv2.INTER_AREA, cv2.COLOR_BGR2RGB = 3, 4
 
 
-def loop_case(th, losses, n_epochs=2, bs=8, S=12, seed=3, lr=1e-4, n_episodes=4, ep_len=26, model_type="custom_cnn", **ctor):
+def loop_case(th, losses, n_epochs=2, bs=8, S=12, seed=3, lr=1e-4, n_episodes=4, ep_len=26, model_type="custom_cnn", balanced=False,
+              **ctor):
     """The UNMODIFIED SRL4robotics.learn() (models/learner.py:259-579: forked loader process, queue, train/validation
     split, best-model checkpoint, state prediction) on the tiny generated dataset of tests/dataset_util.py."""
     import tempfile
@@ -366,6 +441,7 @@ def loop_case(th, losses, n_epochs=2, bs=8, S=12, seed=3, lr=1e-4, n_episodes=4,
         os.chdir(tmp)
         os.makedirs("logs/run", exist_ok=True)
         RLn.DISPLAY_PLOTS, RLn.N_EPOCHS, RLn.BATCH_SIZE, RLn.VALIDATION_SIZE = False, n_epochs, bs, 0.2
+        RLn.BALANCED_SAMPLING = balanced  # (the episode prior's partner draw, train.py --balanced-sampling)
         srl = RLn.SRL4robotics(S, model_type=model_type, seed=seed, learning_rate=lr, cuda=False, losses=losses,
                                n_actions=6, log_folder="logs/run", **ctor)
         loss_history, states, pairs = srl.learn(paths, actions, rewards, starts)
@@ -378,6 +454,8 @@ def loop_case(th, losses, n_epochs=2, bs=8, S=12, seed=3, lr=1e-4, n_episodes=4,
         cfg = dict(losses=losses, n_epochs=n_epochs, bs=bs, S=S, seed=seed, lr=lr, n_episodes=n_episodes, ep_len=ep_len, ctor=ctor)
         if model_type != "custom_cnn":  # (the conv cases' config strings stay byte-identical)
             cfg["model_type"] = model_type
+        if balanced:
+            cfg["balanced"] = True
         out["config"] = np.array(json.dumps(cfg))
         return out
     finally:
@@ -391,7 +469,10 @@ LOOP_CASES = {"loop_aeif": dict(losses=["autoencoder", "inverse", "forward"]),
               "loop_ae_reward": dict(losses=["autoencoder", "reward"], n_epochs=1, seed=5, l2_reg=1e-4),
               # --model-type mlp / linear (reference modules.py:53-69)
               "loop_mlp_ae": dict(losses=["autoencoder"], model_type="mlp"),
-              "loop_linear_aeif": dict(losses=["autoencoder", "inverse", "forward"], model_type="linear")}
+              "loop_linear_aeif": dict(losses=["autoencoder", "inverse", "forward"], model_type="linear"),
+              # the reward-prior / episode-prior losses (losses.py:290-359): every step draws its partners from the global numpy RNG
+              "loop_if_rp_ep": dict(losses=["inverse", "forward", "reward-prior", "episode-prior"]),
+              "loop_mlp_rp_ep_bal": dict(losses=["inverse", "reward-prior", "episode-prior"], model_type="mlp", balanced=True)}
 
 
 def run_loop_child(name):
@@ -498,6 +579,19 @@ def main():
                                                                model_type=mt)))
     save("trace_mlp_ae_l1l2_b2", lambda: dense_subs(step_case(th, ref_pre, SRLModules, RL, ["autoencoder"], B=2, n_steps=3, lr=1e-4,
                                                               l1_reg=1e-5, l2_reg=1e-4, model_type="mlp")))
+    # (8) the reward-prior and episode-prior losses (losses.py:290-359): partner draws, discriminator init, single steps, a trace
+    save("prior_kats", lambda: prior_kats(th))
+    save("step_if_rp_ep_b4", lambda: step_case(th, ref_pre, SRLModules, RL, ["inverse", "forward", "reward-prior", "episode-prior"],
+                                               B=4))
+    save("step_ae_rp_b4", lambda: step_case(th, ref_pre, SRLModules, RL, ["autoencoder", "reward-prior"], B=4))
+    save("step_mlp_vae_ep_bal_b4", lambda: dense_subs(step_case(th, ref_pre, SRLModules, RL, ["vae", "episode-prior"], B=4,
+                                                                model_type="mlp", balanced=True)))
+    save("step_linear_if_ep_b4", lambda: dense_subs(step_case(th, ref_pre, SRLModules, RL, ["inverse", "forward", "episode-prior"],
+                                                              B=4, model_type="linear")))
+    rsplit = OD([("autoencoder", 120), ("inverse", 80), ("reward-prior", -1)])
+    save("step_split_ae_rp_b4", lambda: step_case(th, ref_pre, SRLModules, RL, list(rsplit.keys()), B=4, split=rsplit))
+    save("trace_if_rp_ep_b4", lambda: step_case(th, ref_pre, SRLModules, RL, ["inverse", "forward", "reward-prior", "episode-prior"],
+                                                B=4, n_steps=4, lr=1e-4, val_steps=(2,)))
     for lname in LOOP_CASES:
         save(lname, lambda: run_loop_child(lname))
 
