@@ -187,7 +187,7 @@ int srlz_conv64_bwd_weight(const float* x, const float* dy, float* dw_ref, float
  * ------------------------------------------------------------------------------------------------------------ */
 typedef struct {
   int n, hi, wi, ho, wo; /* NHWC activations: x [n,hi,wi,cin] -> y [n,ho,wo,cout] */
-  int cin, cout;         /* multiples of 64 */
+  int cin, cout;         /* multiples of 64; cin a power of two from 64 to 512 (every entry point refuses anything else) */
   int ksize, stride, pad; /* (3, 1|2, 1) or (1, 2, 0) */
   int groups;            /* BatchNorm groups batched along n (0 / 1 = one), as in srlz_conv64_desc: the launch is the union of
                             `groups` independent trunk calls — the anchor / positive / negative views of obs and next_obs of one

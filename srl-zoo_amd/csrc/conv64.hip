@@ -2717,6 +2717,9 @@ static int check_convn(const srlz_convn_desc* d) {
   SRLZ_REQUIRE(d != nullptr, SRLZ_ERR_NULL, "convn: null descriptor");
   SRLZ_REQUIRE(d->n > 0 && d->cin > 0 && d->cout > 0 && d->cin % 64 == 0 && d->cout % 64 == 0, SRLZ_ERR_BAD_DESC,
                "convn: channels must be multiples of 64 (cin=%d cout=%d)", d->cin, d->cout);
+  // (the staging addresses a pixel's channels by a shift, the fused operand's coefficients of all input-channel blocks sit in 4 KB of LDS)
+  SRLZ_REQUIRE((d->cin & (d->cin - 1)) == 0 && d->cin <= 512, SRLZ_ERR_BAD_DESC,
+               "convn: %d input channels (a power of two from 64 to 512)", d->cin);
   SRLZ_REQUIRE(d->groups >= 0 && (d->groups <= 1 || d->n % d->groups == 0), SRLZ_ERR_BAD_DESC,
                "convn: n = %d is not a multiple of groups = %d", d->n, d->groups);
   const bool k3 = d->ksize == 3 && d->pad == 1 && (d->stride == 1 || d->stride == 2);
@@ -2772,7 +2775,6 @@ extern "C" int srlz_convn_fwd(const float* x, const float* wpack, float* y, floa
   SRLZ_MAX_LDS(convN_fwd_kernel, lds);
   int cshift = 6;
   while ((1 << cshift) < d->cin) ++cshift;
-  SRLZ_REQUIRE((1 << cshift) == d->cin && d->cin <= 512, SRLZ_ERR_BAD_DESC, "convn: %d input channels (a power of two from 64 to 512)", d->cin);
   // (the row table keeps pixel indices in 28 bits, the staging 32-bit float offsets)
   // (per BatchNorm group: P.N images)
   SRLZ_REQUIRE((long long)P.N * d->hi * d->wi * d->cin < (1LL << 32) && (long long)P.N * d->hi * d->wi < (1LL << 28), SRLZ_ERR_BAD_DESC,
