@@ -247,7 +247,11 @@ __device__ __forceinline__ void stage_rows(float* __restrict__ lds, const float*
   constexpr int RP = NTHREADS / 16;  // rows per pass
   // (true divisions: with the uniform divisors hipcc keeps one reciprocal per kernel, and fastdiv here measured 0.5 % SLOWER in
   // conv64_fwd_kernel — unlike in rows64_load, where it is worth 1.5 % of the weight-gradient ring)
-  const int sa = RP / PW, sb = RP - sa * PW;
+  // a pass advances RP grid positions = sn images + sa rows + sb columns (sa < PH, sb < PW): one carry per digit below is then enough
+  // on any grid — with sa = RP / PW alone a grid of fewer than RP / PW + 1 rows (maps of a few pixels, several images) carried past
+  // two images at once and the rows behind the first pass were staged from the wrong pixels
+  const int sn = RP / PHW, srem = RP - sn * PHW;
+  const int sa = srem / PW, sb = srem - sa * PW;
   // shift by one image so the first rows of the first tile (negative q) stay non-negative: n1 = n + 1
   const int qq = qstart + (t >> 4) + PHW;
   int n1 = qq / PHW;
@@ -286,7 +290,7 @@ __device__ __forceinline__ void stage_rows(float* __restrict__ lds, const float*
       const size_t off = (ok ? ((size_t)((n1 - 1) * H + y) * W + x) * cstride : (size_t)0) + coff + slot * 4;
       v[j] = *(const f32x4*)(src + off);
       if (BWD) { yv[j] = *(const f32x4*)(f.y + off); offs[j] = (unsigned)off; }
-      b += sb; a += sa;
+      b += sb; a += sa; n1 += sn;
       if (b >= PW) { b -= PW; ++a; }
       if (a >= PH) { a -= PH; ++n1; }
     }
@@ -1966,7 +1970,9 @@ __device__ __forceinline__ void rows64_load(f32x4 (&v)[NJ], unsigned& okmask, co
   const int cy = cls >> 1, cx = cls & 1;
   const int PHW = PH * PW;
   // (fastdiv: three true divisions here were ~120 VALU instructions per call — per 64-position chunk and thread)
-  const int sa = fastdiv(16, gd.mPW, gd.sPW), sb = 16 - sa * PW;
+  // (16 positions = sn images + sa rows + sb columns, as in stage_rows: one carry per digit on any grid)
+  const int sn = fastdiv(16, gd.mPHW, gd.sPHW), srem = 16 - sn * PHW;
+  const int sa = fastdiv(srem, gd.mPW, gd.sPW), sb = srem - sa * PW;
   const int qq = qstart + (t >> 4) + PHW;  // shifted by one image: non-negative for the first rows of the first chunk
   int n1 = fastdiv(qq, gd.mPHW, gd.sPHW);
   int rem = qq - n1 * PHW;
@@ -1983,7 +1989,7 @@ __device__ __forceinline__ void rows64_load(f32x4 (&v)[NJ], unsigned& okmask, co
       okmask |= (ok ? 1u : 0u) << j;
       if (ok) v[j - J0] = *(const f32x4*)(src + (mad_u24(mad_u24((unsigned)(n1 - 1), H, (unsigned)y), W, (unsigned)x) * 64u + (unsigned)(slot * 4)));
     }
-    b += sb; a += sa;
+    b += sb; a += sa; n1 += sn;
     if (b >= PW) { b -= PW; ++a; }
     if (a >= PH) { a -= PH; ++n1; }
   }

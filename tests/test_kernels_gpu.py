@@ -41,6 +41,7 @@ def out_size(hi, s, p, t):
 
 CONV64 = [(3, 56, 1, 1, 0), (3, 27, 2, 1, 0), (5, 6, 2, 0, 1), (3, 13, 2, 0, 1), (2, 27, 2, 0, 1), (2, 55, 2, 0, 1),
           (1, 9, 1, 1, 0),
+          (3, 3, 1, 1, 0), (4, 2, 2, 0, 1),  # a grid of fewer rows than 16 / PW + 1 holding several images: the staging walk's carries
           (1, 80, 1, 1, 0)]  # 128 + 2 * 82 + 2 = 294 rows per tile: the row table's second batch of passes (rowtab_passes = 32)
 
 

@@ -18,7 +18,9 @@ def out_size(hi, s, p, t):
 
 
 def get_program(cabi, n, hi, s, p, t, backward):
-    d = cabi.Conv64Desc(n, hi, hi, out_size(hi, s, p, t), out_size(hi, s, p, t), 3, s, p, t)
+    """hi: one number for a square map, or (hi, wi)."""
+    hi, wi = hi if isinstance(hi, tuple) else (hi, hi)
+    d = cabi.Conv64Desc(n, hi, wi, out_size(hi, s, p, t), out_size(wi, s, p, t), 3, s, p, t)
     buf = (ctypes.c_int * 64)()
     cnt = cabi.conv64_debug_program(d, backward, buf, 64)
     assert cnt == 48, cabi.error_text()
@@ -216,7 +218,8 @@ def test_row_tables_address_the_rows_the_program_means(cabi, hi, s, p, t):
 
 
 def test_programs_for_random_shapes(cabi):
-    """Beyond the network's own layers: random sizes (odd / even, rectangular inputs are square here by ABI), both strides,
+    """Beyond the network's own layers: random SQUARE sizes (odd / even; the ABI takes height and width separately — include/srlz.h,
+    srlz_conv64_desc — and test_rectangular_programs below holds hi != wi), both strides,
     padded and unpadded, plain and transposed — forward and data-gradient programs against torch, plus the structural
     invariants the kernels rely on (a zero row/column behind every negative offset, span within the LDS ring)."""
     rs = np.random.RandomState(2024)
@@ -264,6 +267,125 @@ def test_programs_for_random_shapes(cabi):
     assert checked >= 20, (checked, declined)
     assert all(not (s == 1 and p == 1 and not t) and not (s == 2 and p == 0 and t) and not (s == 2 and p == 1 and not t)
                for (_, s, p, t) in declined), "a geometry of the network's own layers was declined: %r" % declined
+
+
+# ---- rectangular maps: hi != wi --------------------------------------------------------------------------------------------------
+# Both orientations of every pair: the maps a 160 x 224 frame leaves in the two conv stacks (conv2 40 x 56, conv3 19 x 27, the four
+# ConvTranspose inputs 4 x 6, 9 x 13, 19 x 27, 39 x 55), odd x even, even x odd, and one axis at its minimum (1 and 2).
+RECT_PAIRS = [(40, 56), (19, 27), (4, 6), (9, 13), (39, 55), (3, 8), (7, 12), (1, 5), (2, 9), (1, 2)]
+RECT_SIZES = [hw for pair in RECT_PAIRS for hw in (pair, pair[::-1])]
+RECT_GEOMETRIES = [(s, p, t) for s in (1, 2) for p in (0, 1) for t in (0, 1)]
+
+
+def _declined(cabi, hi, wi, s, p, t):
+    """None when the shape has no output; else (forward program declined, data-gradient program declined)."""
+    ho, wo = out_size(hi, s, p, t), out_size(wi, s, p, t)
+    if ho < 1 or wo < 1:
+        return None
+    d = cabi.Conv64Desc(2, hi, wi, ho, wo, 3, s, p, t)
+    buf = (ctypes.c_int * 64)()
+    return tuple(cabi._lib.srlz_conv64_debug_program(ctypes.byref(d), b, buf, 64) != 48 for b in (0, 1))
+
+
+def _check_zero_behind_negative_offsets(P):
+    """A tap whose offset steps one grid column (row) back wraps, for the first column (row) of the grid, onto the LAST column of the
+    previous row (the last row of the previous image): that column (row) must lie outside the source for every source class that
+    steps back, so that the wrapped read is a zero.  A tap's offset is dy[ky] * PW + dx[kx] with dy, dx in {-1, 0, 1} (build_program:
+    one grid offset per kernel row and per kernel column); a 2-column grid leaves dx = -1 / +1 undecided from the offsets alone, and
+    then one consistent reading must hold."""
+    import itertools
+    taps = P["taps"]
+    readings = [(dy, dx) for dy in itertools.product((-1, 0, 1), repeat=3) for dx in itertools.product((-1, 0, 1), repeat=3)
+                if all(dy[w // 3] * P["PW"] + dx[w % 3] == off for (_, _, off, w) in taps)]
+    assert readings, (P["PW"], taps)
+
+    def holds(dy, dx):
+        for (c, _, _, w) in taps:
+            if dx[w % 3] < 0 and (P["PW"] - 1) * P["ss"] + (c & 1) < P["Ws"]:
+                return False
+            if dy[w // 3] < 0 and (P["PH"] - 1) * P["ss"] + (c >> 1) < P["Hs"]:
+                return False
+        return True
+    assert any(holds(dy, dx) for (dy, dx) in readings), (P["PH"], P["PW"], P["Hs"], P["Ws"], taps)
+    assert len(readings) == 1 or P["PW"] == 2
+
+
+@pytest.mark.parametrize("hi,wi", RECT_SIZES)
+def test_rectangular_programs(cabi, hi, wi):
+    """The virtual-grid programs for hi != wi, both strides, padded and unpadded, plain and transposed: forward and data-gradient
+    programs interpreted against torch's conv2d / conv_transpose2d and autograd, the structural invariants of
+    test_programs_for_random_shapes (a zero row / column behind every negative offset, the span within the LDS ring) and the tap
+    grouping the weight-gradient kernels rely on.  A geometry is declined or accepted for BOTH orientations of a pair; the only
+    declined geometries are the unpadded stride-1 ones (conv: the data gradient needs offsets of -2 rows; convT: its forward does),
+    which no layer of the network has."""
+    rs = np.random.RandomState(hi * 100 + wi)
+    N, C = 2, 2
+    checked = 0
+    for (s, p, t) in RECT_GEOMETRIES:
+        dec = _declined(cabi, hi, wi, s, p, t)
+        assert dec == _declined(cabi, wi, hi, s, p, t), ("declined in one orientation only", hi, wi, s, p, t)
+        if dec is None:
+            assert not t and min(hi, wi) + 2 * p < 3  # (no output position at all: a 3x3 window does not fit)
+            continue
+        if any(dec):
+            assert s == 1 and p == 0 and dec == ((False, True) if not t else (True, False)), (hi, wi, s, p, t, dec)
+            continue
+        ho, wo = out_size(hi, s, p, t), out_size(wi, s, p, t)
+        x = rs.randn(N, hi, wi, C)
+        Wg = rs.randn(9, C, C)
+        P = get_program(cabi, N, (hi, wi), s, p, t, 0)
+        assert (P["Hs"], P["Ws"], P["Hd"], P["Wd"]) == (hi, wi, ho, wo)
+        got = interpret(P, x, Wg)
+        xt = torch.from_numpy(x).permute(0, 3, 1, 2).requires_grad_(True)
+        if t:
+            w = torch.from_numpy(Wg.reshape(3, 3, C, C)).permute(2, 3, 0, 1).contiguous()
+            y = F.conv_transpose2d(xt, w, stride=s, padding=p)
+        else:
+            w = torch.from_numpy(Wg.reshape(3, 3, C, C)).permute(3, 2, 0, 1).contiguous()
+            y = F.conv2d(xt, w, stride=s, padding=p)
+        assert got.shape == (N, ho, wo, C)
+        np.testing.assert_allclose(got, y.detach().permute(0, 2, 3, 1).numpy(), rtol=1e-10, atol=1e-10)
+        dy = rs.randn(N, ho, wo, C)
+        y.backward(torch.from_numpy(dy).permute(0, 3, 1, 2))
+        Pb = get_program(cabi, N, (hi, wi), s, p, t, 1)
+        assert (Pb["Hs"], Pb["Ws"], Pb["Hd"], Pb["Wd"]) == (ho, wo, hi, wi)
+        gotb = interpret(Pb, dy, Wg.transpose(0, 2, 1))
+        np.testing.assert_allclose(gotb, xt.grad.permute(0, 2, 3, 1).numpy(), rtol=1e-10, atol=1e-10)
+        for prog in (P, Pb):
+            assert prog["span"] + 64 <= 256 or len(set(c for (c, _, _, _) in prog["taps"])) > 1 or prog["PW"] > 95
+            assert prog["min_off"] <= 0 <= prog["min_off"] + prog["span"]
+            assert prog["span"] <= 2 * prog["PW"] + 2  # (rows of PW positions: a wide map costs LDS rows, a tall one does not)
+            _check_zero_behind_negative_offsets(prog)
+            key = [(c, d) for (c, d, _, _) in prog["taps"]]
+            if prog["s2"]:
+                assert key[0] == key[1] == key[2] == key[3] and key[4] == key[5] and key[6] == key[7] and len(set(key)) == 4
+            else:
+                assert len(set(key)) == 1
+            assert sorted(w_ for (_, _, _, w_) in prog["taps"]) == list(range(9))
+        checked += 1
+    assert checked >= 5, (hi, wi, checked)  # (of 8 geometries: 2 are declined, a 1-row map has no unpadded convolution)
+
+
+@pytest.mark.parametrize("hi,wi", [(40, 56), (56, 40), (19, 27), (27, 19), (4, 6), (6, 4), (3, 8), (8, 3)])
+def test_rectangular_row_tables(cabi, hi, wi):
+    """test_row_tables_address_the_rows_the_program_means on hi != wi: the entry format as RESTATED here (_rowtab_entry, a Python copy of
+    rowtab_build's arithmetic) names the pixel the program means when Hs != Ws and PH != PW.  This pins the format and the program's
+    geometry, not the device code: the table the kernels build is exercised by tests/test_rect_kernels_gpu.py."""
+    for (s, p, t) in ((1, 1, 0), (2, 1, 0), (2, 0, 1)):
+        for backward in (0, 1):
+            P = get_program(cabi, 3, (hi, wi), s, p, t, backward)
+            PH, PW = P["PH"], P["PW"]
+            total = P["N"] * PH * PW
+            for q in range(P["min_off"], total + P["span"]):
+                e = _rowtab_entry(P, q)
+                n, rem = divmod(q, PH * PW) if q >= 0 else (-1, 0)
+                a, b = rem // PW, rem % PW
+                for c in sorted(set(c for (c, _, _, _) in P["taps"])):
+                    y, x = a * P["ss"] + (c >> 1), b * P["ss"] + (c & 1)
+                    inside = 0 <= q < total and y < P["Hs"] and x < P["Ws"]
+                    assert bool((e >> c) & 1) == inside, (backward, q, c)
+                    if inside:
+                        assert (e >> 4) + (c >> 1) * P["Ws"] + (c & 1) == (n * P["Hs"] + y) * P["Ws"] + x, (backward, q, c)
 
 
 def test_conv1_weight_gradient_tap_table_is_a_conflict_free_deal():
