@@ -661,6 +661,22 @@ int srlz_comm_allreduce_f32(float* buf, long long n, srlz_stream_t stream);
 int srlz_comm_destroy(void);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The supervised baseline (csrc/supervised.hip).  fp32 tensors, row-major; fixed summation order, no atomics.
+ * ------------------------------------------------------------------------------------------------------------ */
+/* nn.MSELoss() of the predicted against the ground-truth states and its gradient in ONE launch (reference
+ * srl_baselines/supervised.py:85,103-104: criterion(pred_states, target_states.detach()); loss.backward()):
+ * loss[0] = fp32(sum((pred - target)^2) / (B * S)), the sum in fp64 in a fixed order and rounded once;
+ * dpred_unit [B, S] = 2 (pred - target) / (B * S), i.e. d loss / d pred for an incoming gradient of 1 (the backward is
+ * srlz_scale_by_scalar of it by the incoming scalar).  No gradient to the target.  Any B >= 1, S >= 1 with B * S <= 2^20; beyond
+ * that SRLZ_ERR_BAD_DESC.  Buffers 16-byte aligned. */
+int srlz_mse_target_fwd(const float* pred, const float* target, int B, int S, float* loss, float* dpred_unit, srlz_stream_t stream);
+/* F.dropout(x, p, training=True) with the caller's mask (reference models/supervised.py:26): y = x * mask / keep with
+ * keep = 1 - p in (0, 1] and mask [rows, cols] uint8 (0 = dropped, anything else = kept), the fp32 operations in that order.
+ * bwd: dx = dy * mask / keep.  Any rows >= 1, cols >= 1; in place allowed.  Eval mode calls neither. */
+int srlz_dropout_fwd(const float* x, const unsigned char* mask, float keep, float* y, int rows, int cols, srlz_stream_t stream);
+int srlz_dropout_bwd(const float* dy, const unsigned char* mask, float keep, float* dx, int rows, int cols, srlz_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Debug / calibration hooks (not on the product path).
  * ------------------------------------------------------------------------------------------------------------ */
 /* Host-only: dump the virtual-grid program of a 64->64 convolution (tests interpret it on the CPU).

@@ -379,7 +379,7 @@ class SRL4robotics(BaseLearner):
         return (RAW_UINT8_INPUT and self.model_type in ("custom_cnn", "mlp", "linear") and self._use_pair
                 and not self._use_graph and not self.use_triplets and not self.use_dae
                 and not (self.use_vae and self.perceptual_similarity_loss)
-                and hotpath._FUSE_RECON and hotpath._FUSE_ENC_IN and hotpath.TAPS is None)
+                and hotpath._FUSE_RECON and hotpath.input_reads_bytes())
 
     def _forwardPair(self, x, next_x, recon=None):
         """(self.model(x), self.model(next_x)) — in that program order for the BatchNorm running statistics — as ONE batched

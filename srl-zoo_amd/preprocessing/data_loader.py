@@ -509,3 +509,62 @@ class DataLoader(object):
                 self.process.terminate()
         except Exception:  # interpreter shutdown: multiprocessing internals may already be gone
             pass
+
+
+class SupervisedDataLoader(DataLoader):
+    """Minibatch stream of the supervised baseline (reference preprocessing/data_loader.py:283-365): ONE frame per sample and, unless
+    `no_targets`, the minibatch's targets — (frames, targets) per item, `frames` alone otherwise — with the reference's ragged
+    minibatch list and, with `shuffle`, one np.random.permutation(n_minibatches) per epoch drawn in the forked producer.
+    (In the reference the base constructor resets the flag after the subclass stored it, :96 after :306, so its loaders never shuffle;
+    here `shuffle` does what it says and the caller decides: srl_baselines/supervised.py::SHUFFLE_MINIBATCHES.)
+
+    :param x_indices: (np.array) indices of observations
+    :param y_values: (np.array) targets for each input value
+    :param images_path: (np.array) Array of path to images
+    :param batch_size: (int)
+    :param n_workers: (int) decoding threads
+    :param no_targets: (bool) only the frames are yielded
+    :param shuffle: (bool) shuffle the minibatch order every epoch
+    :param infinite_loop: (bool) restart after each epoch
+    :param max_queue_len: (int) minibatches prepared ahead
+    :param raw_uint8: as DataLoader's; the default "planar" ships the decoded bytes in the reference's [B, C, W, H] layout
+    """
+
+    def __init__(self, x_indices, y_values, images_path, batch_size, n_workers=1, no_targets=False,
+                 shuffle=False, infinite_loop=True, max_queue_len=4, raw_uint8="planar"):
+        minibatchlist, targets = self.createMinibatchList(x_indices, y_values, batch_size)
+        # (set BEFORE the base class forks the producer, which reads them)
+        self.no_targets = no_targets
+        self.targets = [np.ascontiguousarray(t) for t in targets]  # ragged: a list, one array per minibatch
+        super(SupervisedDataLoader, self).__init__(minibatchlist, images_path, n_workers=n_workers, infinite_loop=infinite_loop,
+                                                   max_queue_len=max_queue_len, is_training=shuffle, raw_uint8=raw_uint8)
+
+    def _run(self):
+        gc.freeze()  # (see DataLoader._run: a forked child of a process that owns a GPU)
+        th.set_num_threads(1)
+        pool = ThreadPoolExecutor(max_workers=max(1, self.n_workers))
+        first = True
+        while first or self.infinite_loop:
+            first = False
+            for minibatch_idx in self._epochOrder():
+                paths = self.images_path[self.minibatchlist[minibatch_idx]]
+                batch = th.cat(list(pool.map(lambda p: self._makeBatchElement(p, raw_uint8=self.raw_uint8), paths)), dim=0)
+                if self.no_targets:
+                    self.queue.put(batch)
+                else:
+                    self.queue.put((batch, th.from_numpy(self.targets[minibatch_idx].copy())))
+            self.queue.put(None)  # end-of-epoch sentinel
+        while True:  # (one-shot loader: the sender outlives the reception of its shared-memory handles)
+            time.sleep(0.05)
+
+    @staticmethod
+    def createMinibatchList(x_indices, y_values, batch_size):
+        """Consecutive slices of at most batch_size indices with their targets; the last one may be shorter, an empty one is dropped.
+        :return: ([np.array], [np.array])"""
+        targets, minibatchlist = [], []
+        for i in range(len(x_indices) // batch_size + 1):
+            excerpt = slice(i * batch_size, min((i + 1) * batch_size, len(x_indices)))
+            if len(x_indices[excerpt]) > 0:
+                minibatchlist.append(x_indices[excerpt])
+                targets.append(y_values[excerpt])
+        return minibatchlist, targets

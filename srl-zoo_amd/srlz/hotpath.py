@@ -45,6 +45,12 @@ _FUSE_ENC_IN = True
 _DEFER_BN_BWD = True
 
 
+def input_reads_bytes(dense=False):
+    """Whether the model's first layer takes the loader's uint8 frames as they are: conv1 inside the fused first block (ops.EncInFn),
+    or the wide input layer of the dense models (ops.DenseInFn, `dense`).  With TAPS on, every route gets the float tensor."""
+    return TAPS is None and (dense or _FUSE_ENC_IN)
+
+
 # ---- the step's reconstruction / generation loss taken inside the last ConvTranspose (ops.DecOutLossFn) -------------------------
 # SRL4robotics._eagerStep opens `with recon_loss_into(target, mean) as req:` around the batched model call; decoder_forward then
 # ends in ONE node that yields the loss scalar (req.loss) and, in place of the reconstruction, the error tensor dec - target

@@ -1234,6 +1234,63 @@ class SqDiffSumFn(Function):
         return da, db, None
 
 
+class MSETargetFn(Function):
+    """nn.MSELoss()(pred, target.detach()) of the supervised baseline (reference srl_baselines/supervised.py:85,103) — loss and
+    d loss / d pred for a unit incoming gradient in ONE launch (srlz_mse_target_fwd); backward scales the latter by the incoming
+    scalar (srlz_scale_by_scalar).  The target carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, target):
+        if target.requires_grad:
+            raise C.SrlzError("mse_target: the target must not require a gradient")
+        pred, target = _check(pred, "mse_target prediction"), _check(target, "mse_target target")
+        if pred.dim() != 2 or pred.shape != target.shape:
+            raise C.SrlzError("mse_target: prediction %s and target %s must be the same [B, S]" % (tuple(pred.shape), tuple(target.shape)))
+        loss = torch.empty((), dtype=torch.float32, device=pred.device)
+        unit = torch.empty_like(pred)
+        C.mse_target_fwd(ptr(pred), ptr(target), pred.shape[0], pred.shape[1], ptr(loss), ptr(unit), stream())
+        ctx.save_for_backward(unit)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        unit, = ctx.saved_tensors
+        dpred = torch.empty_like(unit)
+        C.scale_by_scalar(ptr(unit), ptr(_check(g, "mse_target gradient")), 1.0, 1.0, ptr(dpred), unit.numel(), stream())
+        return dpred, None
+
+
+def mse_target(pred, target):
+    return MSETargetFn.apply(pred, target)
+
+
+class DropoutFn(Function):
+    """F.dropout(x, p, training=True) (reference models/supervised.py:26) with the mask the caller drew: y = x * mask / (1 - p),
+    dx = dy * mask / (1 - p) (srlz_dropout_fwd / srlz_dropout_bwd).  mask: uint8 [rows, cols] on x's device."""
+
+    @staticmethod
+    def forward(ctx, x, mask, p):
+        x = _check(x, "dropout input")
+        if mask.dtype != torch.uint8 or mask.device != x.device or tuple(mask.shape) != tuple(x.shape) or x.dim() != 2:
+            raise C.SrlzError("dropout: the mask must be a uint8 tensor of the input's [rows, cols] on its device")
+        if not 0.0 <= p < 1.0:
+            raise C.SrlzError("dropout: p = %r must lie in [0, 1)" % (p,))
+        mask = mask if mask.is_contiguous() else mask.contiguous()
+        y = torch.empty_like(x)
+        C.dropout_fwd(ptr(x), ptr(mask), 1.0 - p, ptr(y), x.shape[0], x.shape[1], stream())
+        ctx.save_for_backward(mask)
+        ctx.keep = 1.0 - p
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        mask, = ctx.saved_tensors
+        dy = _check(dy, "dropout dy")
+        dx = torch.empty_like(dy)
+        C.dropout_bwd(ptr(dy), ptr(mask), ctx.keep, ptr(dx), dy.shape[0], dy.shape[1], stream())
+        return dx, None, None
+
+
 def weighted(loss, weight):
     """weight * loss — what every loss function of the reference returns (losses/losses.py:102-256; the trainer itself reads the
     terms from the LossManager) — as one HIP launch: 0 + weight * loss with a separately rounded product is exactly that."""
