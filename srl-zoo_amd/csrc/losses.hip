@@ -404,11 +404,15 @@ struct ScalarList {
   int n;
 };
 __global__ void weighted_total_kernel(const ScalarList L, float* __restrict__ total, float* __restrict__ tail) {
+  // no contraction in this body: HIP's __fadd_rn / __fmul_rn are plain + and *, and under the default -ffp-contract=fast the compiler
+  // made one v_fmac_f32 of them — the product lost its own rounding and the total was an ulp off Python's sum
+#pragma clang fp contract(off)
   if (threadIdx.x != 0) return;
   float t = 0.f;
   for (int i = 0; i < L.n; ++i) {
     const float l = *L.p[i];
-    t = __fadd_rn(t, __fmul_rn(L.w[i], l));
+    const float wl = L.w[i] * l;
+    t = t + wl;
     if (tail) tail[1 + i] = l;
   }
   *total = t;
