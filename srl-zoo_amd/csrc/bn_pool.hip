@@ -195,25 +195,6 @@ __global__ __launch_bounds__(256) void bn_relu_pool_fwd_kernel(const float* __re
     }
 }
 
-// Per-block combine of the 16 pixel-rows' fp64 partial sums; partial[block][128] (fp64): [0,64) s1, [64,128) s2.
-// The two BatchNorm-backward sums feed dy = scale*(dz - mean(dz) - xhat*mean(dz*xhat)): an error in either mean is a
-// per-channel CONSTANT added to every dy element, which the following weight-gradient sums coherently over all
-// (non-negative, post-ReLU) inputs.  fp32 accumulation here costs 1e-3..1e-2 of relative accuracy in dW; fp64 is free
-// in an HBM-bound kernel.
-__device__ __forceinline__ void block_reduce_store(const double (&s1)[4], const double (&s2)[4], double* __restrict__ partial) {
-  __shared__ double sm[16][128];
-  const int c4 = threadIdx.x & 15, prow = threadIdx.x >> 4;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { sm[prow][c4 * 4 + j] = s1[j]; sm[prow][64 + c4 * 4 + j] = s2[j]; }
-  __syncthreads();
-  if (threadIdx.x < 128) {
-    double s = 0.0;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s += sm[r][threadIdx.x];
-    partial[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 128 + threadIdx.x] = s;  // (blockIdx.y = BatchNorm group)
-  }
-}
-
 // ---- backward, stage 1: per-channel sums of dz and dz*xhat over the pooled outputs (dz lives at the argmax) ----
 // partial[block][128]: [0,64) sum dz, [64,128) sum dz*xhat
 __global__ __launch_bounds__(256) void bn_relu_pool_bwd_reduce(const float* __restrict__ y, const float* __restrict__ bnp,
@@ -228,10 +209,7 @@ __global__ __launch_bounds__(256) void bn_relu_pool_bwd_reduce(const float* __re
   // z = scale*v + shift at that position, so xhat = ((z - shift)/scale - mean)*invstd needs no access to y — unless
   // `pooled` is not supplied or scale is (almost) 0, where v is gathered from y (one scattered 4-byte read per element).
   const int c4 = threadIdx.x & 15;
-  const f32x4 mean = *(const f32x4*)(bnp + c4 * 4);
-  const f32x4 invstd = *(const f32x4*)(bnp + 64 + c4 * 4);
-  const f32x4 sc = *(const f32x4*)(bnp + 128 + c4 * 4);
-  const f32x4 sh = *(const f32x4*)(bnp + 192 + c4 * 4);
+  const auto [mean, invstd, sc, sh] = load_bn_quads(bnp, c4);
   double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
   // block b walks pooled rows b, b + gridDim.x, ... (row = n*HP + py); 16 pixel-lanes x 16 channel-quads per block
   for (int lrow = blockIdx.x; lrow < N * HP; lrow += gridDim.x) {
@@ -277,7 +255,7 @@ __global__ __launch_bounds__(256) void bn_relu_pool_bwd_reduce(const float* __re
       }
     }
   }
-  block_reduce_store(s1, s2, partial);
+  bn_bwd_combine_store(s1, s2, partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 128);  // (blockIdx.y = BatchNorm group)
 }
 
 // Per group g: sums[g*128 + 0..64) = sum dz, sums[g*128 + 64..128) = sum dz*xhat; dbeta / dgamma = their totals over the groups
@@ -330,10 +308,7 @@ __global__ __launch_bounds__(256) void bn_relu_pool_bwd_apply(const float* __res
     const int n = brow / HB, by = brow - n * HB;
     bnp += (n / npg) * 256;   // this image's BatchNorm group (npg images per group)
     sums += (n / npg) * 128;
-    const f32x4 mean = *(const f32x4*)(bnp + c4 * 4);
-    const f32x4 invstd = *(const f32x4*)(bnp + 64 + c4 * 4);
-    const f32x4 sc = *(const f32x4*)(bnp + 128 + c4 * 4);
-    const f32x4 sh = *(const f32x4*)(bnp + 192 + c4 * 4);
+    const auto [mean, invstd, sc, sh] = load_bn_quads(bnp, c4);
     // Every load of the thread goes out up front, branch-free (clamped address + mask), and is waited for once before the first
     // store: with loads inside the bounds branches the compiler serialises them, and a load consumed after a conditional store
     // waits for that store.
@@ -443,10 +418,7 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_reduce(const float* __restric
   y += (size_t)blockIdx.y * pixels * 64;
   da += (size_t)blockIdx.y * pixels * 64;
   const int c4 = threadIdx.x & 15;
-  const f32x4 mean = *(const f32x4*)(bnp + c4 * 4);
-  const f32x4 invstd = *(const f32x4*)(bnp + 64 + c4 * 4);
-  const f32x4 sc = *(const f32x4*)(bnp + 128 + c4 * 4);
-  const f32x4 sh = *(const f32x4*)(bnp + 192 + c4 * 4);
+  const auto [mean, invstd, sc, sh] = load_bn_quads(bnp, c4);
   double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
   for (long long pix = (long long)blockIdx.x * 16 + (threadIdx.x >> 4); pix < pixels; pix += (long long)gridDim.x * 16) {
     const f32x4 v = *(const f32x4*)(y + pix * 64 + c4 * 4);
@@ -457,7 +429,7 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_reduce(const float* __restric
       if (z > 0.f) { s1[j] += (double)d[j]; s2[j] += (double)(d[j] * ((v[j] - mean[j]) * invstd[j])); }
     }
   }
-  block_reduce_store(s1, s2, partial);
+  bn_bwd_combine_store(s1, s2, partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 128);  // (blockIdx.y = BatchNorm group)
 }
 
 __global__ __launch_bounds__(256) void bn_relu_bwd_apply(const float* __restrict__ y, const float* __restrict__ bnp,
@@ -473,10 +445,7 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_apply(const float* __restrict
   const long long total = pixels * 16;
   for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < total; id += (long long)gridDim.x * blockDim.x) {
     const int c4 = (int)(id & 15);
-    const f32x4 mean = *(const f32x4*)(bnp + c4 * 4);
-    const f32x4 invstd = *(const f32x4*)(bnp + 64 + c4 * 4);
-    const f32x4 sc = *(const f32x4*)(bnp + 128 + c4 * 4);
-    const f32x4 sh = *(const f32x4*)(bnp + 192 + c4 * 4);
+    const auto [mean, invstd, sc, sh] = load_bn_quads(bnp, c4);
     const f32x4 v = *(const f32x4*)(y + id * 4);
     const f32x4 d = *(const f32x4*)(da + id * 4);
     f32x4 o;
@@ -551,11 +520,9 @@ extern "C" int srlz_bn_finalize(const float* stats_partial, int n_partials, int 
   double* staged = (double*)ws;
   const int per = n_partials / G;
   const int g = stage_blocks(per);  // per group exactly what a single-group call uses: results are bit-identical to G calls
-  hipLaunchKernelGGL(reduce_rows_kernel<float>, dim3(g, G), dim3(256), 0, as_stream(stream), stats_partial, per, staged);
-  SRLZ_LAUNCHED();
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(1), dim3(1024), 0, as_stream(stream), (const double*)staged, g, (double)count,
-                     gamma, beta, eps, momentum, repeat, running_mean, running_var, bnp, batch_stat, G, num_batches_tracked);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(reduce_rows_kernel<float>, dim3(g, G), dim3(256), 0, as_stream(stream), stats_partial, per, staged);
+  SRLZ_LAUNCH(bn_finalize_kernel, dim3(1), dim3(1024), 0, as_stream(stream), (const double*)staged, g, (double)count, gamma, beta, eps,
+              momentum, repeat, running_mean, running_var, bnp, batch_stat, G, num_batches_tracked);
   return 0;
 }
 
@@ -580,11 +547,9 @@ extern "C" int srlz_bn_finalize_chunks(const float* stats_partial, int tiles, in
   // (chunk, group) pair is staged with exactly the geometry a single-group call uses, so G batched calls = G separate calls bit for bit
   const int per = tiles / G;
   const int g = stage_blocks(per);
-  hipLaunchKernelGGL(reduce_rows_kernel<float>, dim3(g, chunks * G), dim3(256), 0, as_stream(stream), stats_partial, per, staged);
-  SRLZ_LAUNCHED();
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(chunks), dim3(1024), 0, as_stream(stream), (const double*)staged, g, (double)count,
-                     gamma, beta, eps, momentum, 1, running_mean, running_var, bnp, (float*)nullptr, G, num_batches_tracked);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(reduce_rows_kernel<float>, dim3(g, chunks * G), dim3(256), 0, as_stream(stream), stats_partial, per, staged);
+  SRLZ_LAUNCH(bn_finalize_kernel, dim3(chunks), dim3(1024), 0, as_stream(stream), (const double*)staged, g, (double)count, gamma, beta, eps,
+              momentum, 1, running_mean, running_var, bnp, (float*)nullptr, G, num_batches_tracked);
   return 0;
 }
 
@@ -601,9 +566,8 @@ __global__ void bn_eval_params_chunks_kernel(const float* gamma, const float* be
 extern "C" int srlz_bn_eval_params_chunks(const float* gamma, const float* beta, const float* running_mean,
                                           const float* running_var, float eps, int chunks, float* bnp, srlz_stream_t stream) {
   SRLZ_REQUIRE(gamma && beta && running_mean && running_var && bnp && chunks >= 1, SRLZ_ERR_NULL, "bn_eval_params_chunks: null pointer");
-  hipLaunchKernelGGL(bn_eval_params_chunks_kernel, dim3(chunks), dim3(64), 0, as_stream(stream), gamma, beta, running_mean,
-                     running_var, eps, bnp);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(bn_eval_params_chunks_kernel, dim3(chunks), dim3(64), 0, as_stream(stream), gamma, beta, running_mean, running_var, eps,
+              bnp);
   return 0;
 }
 
@@ -639,9 +603,8 @@ extern "C" int srlz_bn_add_relu(const float* a, const float* a_bnp, const float*
   SRLZ_REQUIRE(a && a_bnp && b && out, SRLZ_ERR_NULL, "bn_add_relu: null pointer");
   const int G = norm_groups(groups);
   SRLZ_REQUIRE(pixels > 0 && chunks >= 1 && pixels % G == 0, SRLZ_ERR_BAD_DESC, "bn_add_relu: %lld pixels, %d groups", pixels, G);
-  hipLaunchKernelGGL(bn_add_relu_kernel, dim3(grid_for(pixels * chunks * 16, 256)), dim3(256), 0, as_stream(stream), a, a_bnp, b,
-                     b_bnp, out, pixels, chunks, pixels / G * chunks * 16);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(bn_add_relu_kernel, dim3(grid_for(pixels * chunks * 16, 256)), dim3(256), 0, as_stream(stream), a, a_bnp, b, b_bnp, out,
+              pixels, chunks, pixels / G * chunks * 16);
   return 0;
 }
 
@@ -657,25 +620,21 @@ __global__ void avgpool_nhwc_kernel(const float* __restrict__ x, float* __restri
 
 extern "C" int srlz_avgpool_nhwc(const float* x, float* out, int n, int hw, int c, srlz_stream_t stream) {
   SRLZ_REQUIRE(x && out && n > 0 && hw > 0 && c > 0, SRLZ_ERR_NULL, "avgpool: bad arguments");
-  hipLaunchKernelGGL(avgpool_nhwc_kernel, dim3(n), dim3(256), 0, as_stream(stream), x, out, hw, c);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(avgpool_nhwc_kernel, dim3(n), dim3(256), 0, as_stream(stream), x, out, hw, c);
   return 0;
 }
 
 extern "C" int srlz_bn_eval_params(const float* gamma, const float* beta, const float* running_mean,
                                    const float* running_var, float eps, float* bnp, srlz_stream_t stream) {
   SRLZ_REQUIRE(gamma && beta && running_mean && running_var && bnp, SRLZ_ERR_NULL, "bn_eval_params: null pointer");
-  hipLaunchKernelGGL(bn_eval_params_kernel, dim3(1), dim3(64), 0, as_stream(stream), gamma, beta, running_mean, running_var,
-                     eps, bnp);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(bn_eval_params_kernel, dim3(1), dim3(64), 0, as_stream(stream), gamma, beta, running_mean, running_var, eps, bnp);
   return 0;
 }
 
 extern "C" int srlz_bn_replay(const float* batch_stat, float momentum, float* running_mean, float* running_var,
                               srlz_stream_t stream) {
   SRLZ_REQUIRE(batch_stat && running_mean && running_var, SRLZ_ERR_NULL, "bn_replay: null pointer");
-  hipLaunchKernelGGL(bn_replay_kernel, dim3(1), dim3(64), 0, as_stream(stream), batch_stat, momentum, running_mean, running_var);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(bn_replay_kernel, dim3(1), dim3(64), 0, as_stream(stream), batch_stat, momentum, running_mean, running_var);
   return 0;
 }
 
@@ -698,8 +657,7 @@ extern "C" int srlz_bn_replay_many(const srlz_bn_replay_item* items, int n, floa
     t.it[i] = items[i];
   }
   for (int i = n; i < SRLZ_BN_REPLAY_MAX; ++i) t.it[i] = items[0];
-  hipLaunchKernelGGL(bn_replay_many_kernel, dim3(n), dim3(64), 0, as_stream(stream), t, momentum);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(bn_replay_many_kernel, dim3(n), dim3(64), 0, as_stream(stream), t, momentum);
   return 0;
 }
 
@@ -713,9 +671,8 @@ extern "C" int srlz_bn_relu_pool_fwd(const float* y, const float* bnp, float* po
   const int gx = (WB * 16 + 255) / 256;
   SRLZ_REQUIRE((long long)gx * d->n * HB <= 0x7fffffffLL && (long long)d->n * (d->h + 4) <= 0x7fffffffLL, SRLZ_ERR_BAD_DESC,
                "pool: %d images of %d x %d are too many for one launch", d->n, d->h, d->w);
-  hipLaunchKernelGGL(bn_relu_pool_fwd_kernel, dim3(gx * d->n * HB), dim3(256), 0, as_stream(stream), y, bnp, pooled, argmax, d->n, d->h,
-                     d->w, d->hp, d->wp, d->pool_pad, d->out_nchw, d->n / norm_groups(d->groups), gx);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(bn_relu_pool_fwd_kernel, dim3(gx * d->n * HB), dim3(256), 0, as_stream(stream), y, bnp, pooled, argmax, d->n, d->h, d->w,
+              d->hp, d->wp, d->pool_pad, d->out_nchw, d->n / norm_groups(d->groups), gx);
   return 0;
 }
 
@@ -732,15 +689,12 @@ static int pool_bwd_sums(const float* y, const float* bnp, const uint8_t* argmax
   const int G = norm_groups(d->groups), npg = d->n / G;
   int nb = npg * d->hp;
   if (nb > RED_BLOCKS / G) nb = RED_BLOCKS / G;
-  hipLaunchKernelGGL(bn_relu_pool_bwd_reduce, dim3(nb, G), dim3(256), 0, st, y, bnp, argmax, dpooled, pooled, partial, npg, d->h, d->w,
-                     d->hp, d->wp, d->pool_pad, d->out_nchw);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(bn_relu_pool_bwd_reduce, dim3(nb, G), dim3(256), 0, st, y, bnp, argmax, dpooled, pooled, partial, npg, d->h, d->w, d->hp,
+              d->wp, d->pool_pad, d->out_nchw);
   int sg = stage_blocks(nb);
   if (sg > STAGE_ROWS / G) sg = STAGE_ROWS / G;
-  hipLaunchKernelGGL(reduce_rows_kernel<double>, dim3(sg, G), dim3(256), 0, st, (const double*)partial, nb, staged);
-  SRLZ_LAUNCHED();
-  hipLaunchKernelGGL(bn_bwd_finalize, dim3(1), dim3(1024), 0, st, (const double*)staged, sg, sums, dgamma, dbeta, G);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(reduce_rows_kernel<double>, dim3(sg, G), dim3(256), 0, st, (const double*)partial, nb, staged);
+  SRLZ_LAUNCH(bn_bwd_finalize, dim3(1), dim3(1024), 0, st, (const double*)staged, sg, sums, dgamma, dbeta, G);
   return 0;
 }
 
@@ -768,9 +722,8 @@ extern "C" int srlz_bn_relu_pool_bwd(const float* y, const float* bnp, const uin
   const int npg = d->n / norm_groups(d->groups);
   const float inv_count = 1.0f / (float)((double)npg * d->h * d->w);
   const int gx = (WB * 16 + 255) / 256;
-  hipLaunchKernelGGL(bn_relu_pool_bwd_apply, dim3(gx * d->n * HB), dim3(256), 0, st, y, bnp, argmax, dpooled, sums, dy,
-                     d->n, d->h, d->w, d->hp, d->wp, d->pool_pad, d->out_nchw, training, inv_count, npg, gx);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(bn_relu_pool_bwd_apply, dim3(gx * d->n * HB), dim3(256), 0, st, y, bnp, argmax, dpooled, sums, dy, d->n, d->h, d->w, d->hp,
+              d->wp, d->pool_pad, d->out_nchw, training, inv_count, npg, gx);
   return 0;
 }
 
@@ -785,16 +738,14 @@ extern "C" int srlz_bn_relu_pool_bwd_apply(const float* y, const float* bnp, con
   const int npg = d->n / norm_groups(d->groups);
   const float inv_count = 1.0f / (float)((double)npg * d->h * d->w);
   const int gx = (WB * 16 + 255) / 256;
-  hipLaunchKernelGGL(bn_relu_pool_bwd_apply, dim3(gx * d->n * HB), dim3(256), 0, as_stream(stream), y, bnp, argmax,
-                     dpooled, sums, dy, d->n, d->h, d->w, d->hp, d->wp, d->pool_pad, d->out_nchw, training, inv_count, npg, gx);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(bn_relu_pool_bwd_apply, dim3(gx * d->n * HB), dim3(256), 0, as_stream(stream), y, bnp, argmax, dpooled, sums, dy, d->n, d->h,
+              d->w, d->hp, d->wp, d->pool_pad, d->out_nchw, training, inv_count, npg, gx);
   return 0;
 }
 
 extern "C" int srlz_bn_relu_fwd(const float* y, const float* bnp, float* a, long long pixels, srlz_stream_t stream) {
   SRLZ_REQUIRE(y && bnp && a, SRLZ_ERR_NULL, "bn_relu_fwd: null pointer");
-  hipLaunchKernelGGL(bn_relu_fwd_kernel, dim3(grid_for(pixels * 16, 256)), dim3(256), 0, as_stream(stream), y, bnp, a, pixels);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(bn_relu_fwd_kernel, dim3(grid_for(pixels * 16, 256)), dim3(256), 0, as_stream(stream), y, bnp, a, pixels);
   return 0;
 }
 
@@ -808,14 +759,11 @@ static int bn_relu_bwd_sums_launch(const float* y, const float* bnp, const float
   const long long ppg = pixels / G;
   int nb = (int)((ppg + 15) / 16);
   if (nb > RED_BLOCKS / G) nb = RED_BLOCKS / G;
-  hipLaunchKernelGGL(bn_relu_bwd_reduce, dim3(nb, G), dim3(256), 0, st, y, bnp, da, partial, ppg);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(bn_relu_bwd_reduce, dim3(nb, G), dim3(256), 0, st, y, bnp, da, partial, ppg);
   int sg = stage_blocks(nb);
   if (sg > STAGE_ROWS / G) sg = STAGE_ROWS / G;
-  hipLaunchKernelGGL(reduce_rows_kernel<double>, dim3(sg, G), dim3(256), 0, st, (const double*)partial, nb, staged);
-  SRLZ_LAUNCHED();
-  hipLaunchKernelGGL(bn_bwd_finalize, dim3(1), dim3(1024), 0, st, (const double*)staged, sg, sums, dgamma, dbeta, G);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(reduce_rows_kernel<double>, dim3(sg, G), dim3(256), 0, st, (const double*)partial, nb, staged);
+  SRLZ_LAUNCH(bn_bwd_finalize, dim3(1), dim3(1024), 0, st, (const double*)staged, sg, sums, dgamma, dbeta, G);
   return 0;
 }
 
@@ -832,10 +780,8 @@ extern "C" int srlz_bn_bwd_finalize_partials(const float* partial, int n_partial
   double* staged = (double*)ws;
   const int per = n_partials / G;
   const int g = stage_blocks(per);
-  hipLaunchKernelGGL(reduce_rows_kernel<float>, dim3(g, G), dim3(256), 0, st, partial, per, staged);
-  SRLZ_LAUNCHED();
-  hipLaunchKernelGGL(bn_bwd_finalize, dim3(1), dim3(1024), 0, st, (const double*)staged, g, sums, dgamma, dbeta, G);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(reduce_rows_kernel<float>, dim3(g, G), dim3(256), 0, st, partial, per, staged);
+  SRLZ_LAUNCH(bn_bwd_finalize, dim3(1), dim3(1024), 0, st, (const double*)staged, g, sums, dgamma, dbeta, G);
   return 0;
 }
 
@@ -857,24 +803,18 @@ extern "C" int srlz_bn_relu_bwd(const float* y, const float* bnp, const float* d
   if (int rc = bn_relu_bwd_sums_launch(y, bnp, da, sums, dgamma, dbeta, ws, pixels, G, st)) return rc;
   const long long ppg = pixels / G;
   const float inv_count = 1.0f / (float)(double)ppg;
-  hipLaunchKernelGGL(bn_relu_bwd_apply, dim3(grid_for(ppg * 16, 256), G), dim3(256), 0, st, y, bnp, da, sums, dy, ppg,
-                     training, inv_count);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(bn_relu_bwd_apply, dim3(grid_for(ppg * 16, 256), G), dim3(256), 0, st, y, bnp, da, sums, dy, ppg, training, inv_count);
   return 0;
 }
 
 extern "C" int srlz_nchw_to_nhwc(const float* src, float* dst, int n, int c, int h, int w, srlz_stream_t stream) {
   SRLZ_REQUIRE(src && dst, SRLZ_ERR_NULL, "nchw_to_nhwc: null pointer");
-  hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(grid_for((long long)n * c * h * w, 256)), dim3(256), 0, as_stream(stream), src,
-                     dst, n, c, h * w);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(nchw_to_nhwc_kernel, dim3(grid_for((long long)n * c * h * w, 256)), dim3(256), 0, as_stream(stream), src, dst, n, c, h * w);
   return 0;
 }
 
 extern "C" int srlz_nhwc_to_nchw(const float* src, float* dst, int n, int c, int h, int w, srlz_stream_t stream) {
   SRLZ_REQUIRE(src && dst, SRLZ_ERR_NULL, "nhwc_to_nchw: null pointer");
-  hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(grid_for((long long)n * c * h * w, 256)), dim3(256), 0, as_stream(stream), src,
-                     dst, n, c, h * w);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(nhwc_to_nchw_kernel, dim3(grid_for((long long)n * c * h * w, 256)), dim3(256), 0, as_stream(stream), src, dst, n, c, h * w);
   return 0;
 }

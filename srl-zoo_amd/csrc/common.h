@@ -39,7 +39,13 @@ int srlz_hip_fail(hipError_t e, const char* what);
     }                                 \
   } while (0)
 
-#define SRLZ_LAUNCHED() SRLZ_HIP(hipGetLastError())
+// Launch, then return the launch's error (a bad LDS request, a grid of 0 ...) from the calling function: a launch that is not checked
+// fails silently and its consumer reads memory nobody wrote.  A templated kernel name with commas goes in parentheses.
+#define SRLZ_LAUNCH(kernel, grid, block, lds_bytes, stream, ...)                 \
+  do {                                                                           \
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, __VA_ARGS__);     \
+    SRLZ_HIP(hipGetLastError());                                                 \
+  } while (0)
 
 static inline hipStream_t as_stream(srlz_stream_t s) { return (hipStream_t)s; }
 
@@ -71,4 +77,68 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+// Sum of v over a block of NWAVES waves in a fixed order (deterministic): fp64 wave sums, one LDS slot per wave, one barrier.
+// Contract: blockDim.x == 64 * NWAVES, EVERY thread of the block calls it, at most once per kernel (the slots are not
+// re-armed); the sums are meant for thread 0.  block_wave_sums_d returns the slots, block_sum_d adds them left to right,
+// ((s0 + s1) + s2) + ..., block_sum_pairs_d as (s0 + s1) + (s2 + s3).
+template <int NWAVES = 4>
+__device__ __forceinline__ const double* block_wave_sums_d(double v) {
+  __shared__ double slots[NWAVES];
+  v = wave_sum_d(v);
+  if ((threadIdx.x & 63) == 0) slots[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return slots;
+}
+
+template <int NWAVES = 4>
+__device__ __forceinline__ double block_sum_d(double v) {
+  const double* s = block_wave_sums_d<NWAVES>(v);
+  double t = s[0];
+#pragma unroll
+  for (int w = 1; w < NWAVES; ++w) t += s[w];
+  return t;
+}
+
+__device__ __forceinline__ double block_sum_pairs_d(double v) {
+  const double* s = block_wave_sums_d<4>(v);
+  return (s[0] + s[1]) + (s[2] + s[3]);
+}
+
+// A thread's four channels (c4 * 4 ..) of a BatchNorm record bnp[256]: [0,64) mean, [64,128) invstd, [128,192) scale, [192,256) shift
+struct BnRec4 { f32x4 mean, invstd, sc, sh; };
+__device__ __forceinline__ BnRec4 load_bn_quads(const float* __restrict__ bnp, int c4) {
+  return {*(const f32x4*)(bnp + c4 * 4), *(const f32x4*)(bnp + 64 + c4 * 4), *(const f32x4*)(bnp + 128 + c4 * 4),
+          *(const f32x4*)(bnp + 192 + c4 * 4)};
+}
+
+// Block combine of the BatchNorm-backward sums.  Contract: 256 threads, thread = (pixel row threadIdx.x >> 4, channel quad
+// threadIdx.x & 15) holding the fp64 sums s1 (dz) and s2 (dz * xhat) of its 4 channels; EVERY thread calls it.  The 16 pixel rows are
+// added in row order r = 0..15 (deterministic) and row[0..64) = s1, row[64..128) = s2 are stored as T.
+// These sums feed dy = scale*(dz - mean(dz) - xhat*mean(dz*xhat)): an error in either mean is a per-channel CONSTANT added to every dy
+// element, which the following weight-gradient sums coherently over all (non-negative, post-ReLU) inputs.  fp32 accumulation here costs
+// 1e-3..1e-2 of relative accuracy in dW; fp64 is free in an HBM-bound kernel.
+template <typename T>
+__device__ __forceinline__ void bn_bwd_combine_store(const double (&s1)[4], const double (&s2)[4], T* __restrict__ row) {
+  __shared__ double sm[16][128];
+  const int c4 = threadIdx.x & 15, prow = threadIdx.x >> 4;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { sm[prow][c4 * 4 + j] = s1[j]; sm[prow][64 + c4 * 4 + j] = s2[j]; }
+  __syncthreads();
+  if (threadIdx.x < 128) {
+    double s = 0.0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s += sm[r][threadIdx.x];
+    row[threadIdx.x] = (T)s;
+  }
+}
+
+// Grid-stride walk over n floats, four at a time: quad(i) for every whole f32x4 (elements 4i .. 4i+3), then one(i) for every element
+// of the tail n & 3.  The buffers behind quad() must be 16-byte aligned.
+template <class F4, class F1>
+__device__ __forceinline__ void for_each_quad(long long n, F4 quad, F1 one) {
+  const long long n4 = n >> 2, stride = (long long)gridDim.x * blockDim.x, first = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  for (long long i = first; i < n4; i += stride) quad(i);
+  for (long long i = n4 * 4 + first; i < n; i += stride) one(i);
 }

@@ -1617,8 +1617,7 @@ __global__ __launch_bounds__(256) void conv64_bnpart_zero_scale_kernel(const flo
   x += (size_t)g * pixels * 64;
   da += (size_t)g * pixels * 64;
   const int c4 = threadIdx.x & 15;
-  const f32x4 mean = *(const f32x4*)(x_bnp + c4 * 4), invstd = *(const f32x4*)(x_bnp + 64 + c4 * 4);
-  const f32x4 sc = *(const f32x4*)(x_bnp + 128 + c4 * 4), sh = *(const f32x4*)(x_bnp + 192 + c4 * 4);
+  const auto [mean, invstd, sc, sh] = load_bn_quads(x_bnp, c4);
   unsigned zmask = 0;
 #pragma unroll
   for (int j = 0; j < 4; ++j) zmask |= (bnpart_zero_scale(sc[j], sh[j]) ? 1u : 0u) << j;
@@ -1635,17 +1634,7 @@ __global__ __launch_bounds__(256) void conv64_bnpart_zero_scale_kernel(const flo
         }
     }
   }
-  __shared__ double sm[16][128];
-  const int prow = threadIdx.x >> 4;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { sm[prow][c4 * 4 + j] = s1[j]; sm[prow][64 + c4 * 4 + j] = s2[j]; }
-  __syncthreads();
-  if (threadIdx.x < 128) {
-    double t = 0.0;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) t += sm[r][threadIdx.x];
-    bnpart[((size_t)g * bn_rows + first_row + blockIdx.x) * 128 + threadIdx.x] = (float)t;
-  }
+  bn_bwd_combine_store(s1, s2, bnpart + ((size_t)g * bn_rows + first_row + blockIdx.x) * 128);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -2448,12 +2437,11 @@ static int launch_fwd(const float* src, const float* wpack, const float* bias, f
     for (int t = 1; t < NTAPS; ++t) one_class = one_class && P.tdst[t] == P.tdst[0];
     if (one_class) {
       SRLZ_MAX_LDS(conv64_dgrad_poolsum_kernel<1>, lds);
-      hipLaunchKernelGGL(conv64_dgrad_poolsum_kernel<1>, dim3(ntiles), dim3(256), lds, st, src, wpack, dst, stats, P, ntiles, *psum);
+      SRLZ_LAUNCH(conv64_dgrad_poolsum_kernel<1>, dim3(ntiles), dim3(256), lds, st, src, wpack, dst, stats, P, ntiles, *psum);
     } else {
       SRLZ_MAX_LDS(conv64_dgrad_poolsum_kernel<2>, lds);
-      hipLaunchKernelGGL(conv64_dgrad_poolsum_kernel<2>, dim3(ntiles), dim3(256), lds, st, src, wpack, dst, stats, P, ntiles, *psum);
+      SRLZ_LAUNCH(conv64_dgrad_poolsum_kernel<2>, dim3(ntiles), dim3(256), lds, st, src, wpack, dst, stats, P, ntiles, *psum);
     }
-    SRLZ_LAUNCHED();
     return 0;
   }
   // 4 waves (32x64 per wave); 8 waves of 32x32 were measured within +-3 % (the kernel is bound by the power-limited matrix
@@ -2461,8 +2449,8 @@ static int launch_fwd(const float* src, const float* wpack, const float* bias, f
 #define SRLZ_FWD_LAUNCH(NWV, BWDV)                                                                                          \
   do {                                                                                                                     \
     SRLZ_MAX_LDS((conv64_fwd_kernel<NWV, BWDV>), lds);                                                                      \
-    hipLaunchKernelGGL((conv64_fwd_kernel<NWV, BWDV>), dim3(ntiles), dim3(NWV * 64), lds, st, src, wpack, bias, dst, stats, \
-                       P, ntiles, src_fuse);                                                                               \
+    SRLZ_LAUNCH((conv64_fwd_kernel<NWV, BWDV>), dim3(ntiles), dim3(NWV * 64), lds, st, src, wpack, bias, dst, stats,        \
+                P, ntiles, src_fuse);                                                                                      \
   } while (0)
   if (src_fuse.y) {
     SRLZ_REQUIRE((long long)P.N * P.Hs * P.Ws * 64 < (1LL << 32), SRLZ_ERR_BAD_DESC,
@@ -2480,14 +2468,12 @@ static int launch_fwd(const float* src, const float* wpack, const float* bias, f
       if (pgrid < 8) pgrid = 8;  // (the XCD walk wants a multiple of 8 workgroups; those without a tile leave at once)
       const size_t plds = (size_t)(TM + P.span) * 256 + 16384 + 6 * TM * 4 + GT_WORDS * 4 + 8 * 64 * 4;
       SRLZ_MAX_LDS(conv64_gather_pipe_kernel, plds);
-      hipLaunchKernelGGL(conv64_gather_pipe_kernel, dim3(pgrid), dim3(GP_THREADS), plds, st, src, wpack, dst, stats, P, ntiles);
-      SRLZ_LAUNCHED();
+      SRLZ_LAUNCH(conv64_gather_pipe_kernel, dim3(pgrid), dim3(GP_THREADS), plds, st, src, wpack, dst, stats, P, ntiles);
       return 0;
     }
     SRLZ_FWD_LAUNCH(4, false);
   }
 #undef SRLZ_FWD_LAUNCH
-  SRLZ_LAUNCHED();
   return 0;
 }
 
@@ -2756,9 +2742,8 @@ extern "C" int srlz_convn_pack_weights(const float* w_ref, float* wpack, const s
   if (int rc = check_convn(d)) return rc;
   SRLZ_REQUIRE(w_ref && wpack, SRLZ_ERR_NULL, "convn_pack: null pointer");
   const long long total = (long long)(d->cin / 64) * (d->cout / 64) * NTAPS * 4096;
-  hipLaunchKernelGGL(convN_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream), w_ref, wpack,
-                     d->cin / 64, d->cout / 64, d->ksize);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(convN_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream), w_ref, wpack, d->cin / 64,
+              d->cout / 64, d->ksize);
   return 0;
 }
 
@@ -2791,9 +2776,8 @@ extern "C" int srlz_convn_fwd(const float* x, const float* wpack, float* y, floa
       if (P.tw[t] == 4) only_tap = t;
     SRLZ_REQUIRE(only_tap >= 0, SRLZ_ERR_BAD_DESC, "convn: no centre tap in the program of a 1x1 convolution");
   }
-  hipLaunchKernelGGL(convN_fwd_kernel, dim3(ntiles, d->cout / 64), dim3(256), lds, as_stream(stream), x, wpack, y, stats_partial, P,
-                     ntiles, d->cin / 64, d->cout / 64, x_bnp, only_tap, cshift);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(convN_fwd_kernel, dim3(ntiles, d->cout / 64), dim3(256), lds, as_stream(stream), x, wpack, y, stats_partial, P, ntiles,
+              d->cin / 64, d->cout / 64, x_bnp, only_tap, cshift);
   return 0;
 }
 
@@ -2803,9 +2787,8 @@ extern "C" int srlz_conv64_pack_weights(const float* w_ref, float* wpack_fwd, fl
                                         const srlz_conv64_desc* d, srlz_stream_t stream) {
   if (int rc = check_desc(d)) return rc;
   SRLZ_REQUIRE(w_ref, SRLZ_ERR_NULL, "conv64_pack: null weights");
-  hipLaunchKernelGGL(conv64_pack_kernel, dim3((NTAPS * 4096 + 255) / 256), dim3(256), 0, as_stream(stream), w_ref,
-                     wpack_fwd, wpack_bwd, d->transposed);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(conv64_pack_kernel, dim3((NTAPS * 4096 + 255) / 256), dim3(256), 0, as_stream(stream), w_ref, wpack_fwd, wpack_bwd,
+              d->transposed);
   return 0;
 }
 
@@ -2904,7 +2887,7 @@ extern "C" int srlz_conv64_bwd_weight(const float* x, const float* dy, float* dw
     launched_grid = wpg * P.G;
     const size_t lds = (size_t)(RING_S2 + 4 * 32) * 256;
     SRLZ_MAX_LDS(conv64_wgrad_ring_s2_kernel, lds);
-    hipLaunchKernelGGL(conv64_wgrad_ring_s2_kernel, dim3(launched_grid), dim3(256), lds, st, x, dy, partial, P, nch, cpw, wpg, x_bnp);
+    SRLZ_LAUNCH(conv64_wgrad_ring_s2_kernel, dim3(launched_grid), dim3(256), lds, st, x, dy, partial, P, nch, cpw, wpg, x_bnp);
   } else if (single_src && gf.y == nullptr && !P.s2 && tk + P.span + tk <= RING_ROWS && tk == 64 &&
              (long long)P.N * P.Hs * P.Ws * 64 < (1LL << 32) && (long long)P.N * P.Hd * P.Wd * 64 < (1LL << 32) &&
              (long long)P.total_q + 2 * P.PHW < (1LL << 31)) {  // (the row tables of the stride-1 kernel: 32-bit offsets)
@@ -2915,28 +2898,26 @@ extern "C" int srlz_conv64_bwd_weight(const float* x, const float* dy, float* dw
     launched_grid = wpg * P.G;
     const size_t lds = (size_t)(RING + 64) * 256 + 2 * 64 * 4;  // ring + gradient rows + the two row tables = 80 KB
     SRLZ_MAX_LDS(conv64_wgrad_ring_kernel, lds);
-    hipLaunchKernelGGL(conv64_wgrad_ring_kernel, dim3(launched_grid), dim3(256), lds, st, x, dy, partial, P, nchunks, cpw, wpg, x_bnp);
+    SRLZ_LAUNCH(conv64_wgrad_ring_kernel, dim3(launched_grid), dim3(256), lds, st, x, dy, partial, P, nchunks, cpw, wpg, x_bnp);
   } else if (wgrad_gather_ok(P) && x_bnp == nullptr && gf.y == nullptr && tk == WG_TK) {
     // stride-2 gather programs (conv3): the software-pipelined kernel; same grid, same partials as conv64_wgrad_kernel<true, 64>
     const size_t lds = (size_t)(WG_TK + P.span + WG_TK) * 256 + (WG_SWORDS + WG_GWORDS) * 4;
     SRLZ_MAX_LDS(conv64_wgrad_gather_kernel, lds);
-    hipLaunchKernelGGL(conv64_wgrad_gather_kernel, dim3(grid), dim3(256), lds, st, x, dy, partial, P, nchunks * P.G);
+    SRLZ_LAUNCH(conv64_wgrad_gather_kernel, dim3(grid), dim3(256), lds, st, x, dy, partial, P, nchunks * P.G);
   } else {
     const size_t lds = wgrad_lds_bytes(P, tk);
     SRLZ_REQUIRE(lds <= 160 * 1024, SRLZ_ERR_BAD_DESC, "conv64 wgrad: chunk needs %zu bytes of LDS", lds);
 #define SRLZ_WGRAD_LAUNCH(S2V, TKV)                                                                                        \
   do {                                                                                                                     \
     SRLZ_MAX_LDS((conv64_wgrad_kernel<S2V, TKV>), lds);                                                                     \
-    hipLaunchKernelGGL((conv64_wgrad_kernel<S2V, TKV>), dim3(grid), dim3(256), lds, st, x, dy, partial, P, nchunks * P.G, xf, gf); \
+    SRLZ_LAUNCH((conv64_wgrad_kernel<S2V, TKV>), dim3(grid), dim3(256), lds, st, x, dy, partial, P, nchunks * P.G, xf, gf);        \
   } while (0)
     if (P.s2) SRLZ_WGRAD_LAUNCH(true, 64);
     else SRLZ_WGRAD_LAUNCH(false, 64);
 #undef SRLZ_WGRAD_LAUNCH
   }
-  SRLZ_LAUNCHED();
-  hipLaunchKernelGGL(conv64_wgrad_reduce, dim3((NTAPS * 4096 + 64 + 255) / 256), dim3(1024), 0, st, partial, launched_grid,
-                     dw_ref, dbias, d->transposed, 0);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(conv64_wgrad_reduce, dim3((NTAPS * 4096 + 64 + 255) / 256), dim3(1024), 0, st, partial, launched_grid, dw_ref, dbias,
+              d->transposed, 0);
   return 0;
 }
 
@@ -3013,16 +2994,13 @@ extern "C" int srlz_conv64_bwd_fused(const float* x, const float* x_bnp, const f
   fb.x = x; fb.x_bnp = x_bnp; fb.wpartial = (float*)ws;
   fb.bnpart = x_bn_bwd_partial; fb.bn_rows = 4 * P.tpg + BNZ_BLOCKS;
   SRLZ_MAX_LDS(conv64_bwd_fused_kernel, lds);
-  hipLaunchKernelGGL(conv64_bwd_fused_kernel, dim3(grid), dim3(GP_THREADS), lds, st, dy, wpack_bwd, dx, P, P.G * P.tpg, gf, fb);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(conv64_bwd_fused_kernel, dim3(grid), dim3(GP_THREADS), lds, st, dy, wpack_bwd, dx, P, P.G * P.tpg, gf, fb);
   // second stage: fixed-order fp64 sum over the workgroups (the partial's bias block sits behind EACH workgroup's taps here)
-  hipLaunchKernelGGL(conv64_wgrad_reduce, dim3((NTAPS * 4096 + 64 + 255) / 256), dim3(1024), 0, st, (const float*)ws, grid, dw_ref, dbias,
-                     1, NTAPS * 4096 + 64);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(conv64_wgrad_reduce, dim3((NTAPS * 4096 + 64 + 255) / 256), dim3(1024), 0, st, (const float*)ws, grid, dw_ref, dbias, 1,
+              NTAPS * 4096 + 64);
   if (x_bn_bwd_partial) {  // the records of the channels the fused kernel cannot sum from the activation (normally: zeros)
-    hipLaunchKernelGGL(conv64_bnpart_zero_scale_kernel, dim3(BNZ_BLOCKS, P.G), dim3(256), 0, st, x, x_bnp, (const float*)dx,
-                       x_bn_bwd_partial, (long long)P.N * P.Hd * P.Wd, fb.bn_rows, 4 * P.tpg);
-    SRLZ_LAUNCHED();
+    SRLZ_LAUNCH(conv64_bnpart_zero_scale_kernel, dim3(BNZ_BLOCKS, P.G), dim3(256), 0, st, x, x_bnp, (const float*)dx, x_bn_bwd_partial,
+                (long long)P.N * P.Hd * P.Wd, fb.bn_rows, 4 * P.tpg);
   }
   return 0;
 }

@@ -651,14 +651,13 @@ int os_fwd_launch(const float* x, const float* w, const float* bias, float* out,
 #define SRLZ_OS_FWD(DECV)                                                                                                       \
   do {                                                                                                                        \
     SRLZ_MAX_LDS((convT_out_os_kernel<NCG, LOSS, TT, DECV>), lds);                                                            \
-    hipLaunchKernelGGL((convT_out_os_kernel<NCG, LOSS, TT, DECV>), dim3(g.grid), dim3(256), lds, st, x, w, bias, out, d->n, d->himg, \
-                       d->wimg, d->hf, d->wf, bnp, os_npg(d), target, dec, loss_partial, d->n / 2 > 0 ? d->n / 2 : 1, lut, g.rows, \
-                       g.nseg, g.nchunk);                                                                                     \
+    SRLZ_LAUNCH((convT_out_os_kernel<NCG, LOSS, TT, DECV>), dim3(g.grid), dim3(256), lds, st, x, w, bias, out, d->n, d->himg,        \
+                d->wimg, d->hf, d->wf, bnp, os_npg(d), target, dec, loss_partial, d->n / 2 > 0 ? d->n / 2 : 1, lut, g.rows,        \
+                g.nseg, g.nchunk);                                                                                            \
   } while (0)
   if constexpr (LOSS) { if (dec) SRLZ_OS_FWD(true); else SRLZ_OS_FWD(false); }
   else SRLZ_OS_FWD(false);
 #undef SRLZ_OS_FWD
-  SRLZ_LAUNCHED();
   return 0;
 }
 
@@ -785,18 +784,15 @@ extern "C" int srlz_convT_out_bwd_fused(const float* dy_nchw, const float* w_ref
     size_t fl = (size_t)4 * ((NCG) * 3 * 8 * RP + 16 * OSP + 192) + ((NCG) > 1 ? (NCG) * 4 * 12 * 64 : 0);                          \
     if (fl < 4 * 64 * 48) fl = 4 * 64 * 48;                                                                                   \
     SRLZ_MAX_LDS((convT_out_os_bwd_kernel<NCG>), fl * 4);                                                                     \
-    hipLaunchKernelGGL((convT_out_os_bwd_kernel<NCG>), dim3(g.grid), dim3(256), fl * 4, st, dy_nchw, w_ref, dx_nhwc, bn_bwd_partial, \
-                       partial, d->n, d->himg, d->wimg, d->hf, d->wf, x_raw, x_bnp, os_npg(d), bias_part, dy_gain_dev,        \
-                       dy_gain_div, dy_gain_coef, g.rows, g.nseg, g.nchunk);                                                  \
+    SRLZ_LAUNCH((convT_out_os_bwd_kernel<NCG>), dim3(g.grid), dim3(256), fl * 4, st, dy_nchw, w_ref, dx_nhwc, bn_bwd_partial,        \
+                partial, d->n, d->himg, d->wimg, d->hf, d->wf, x_raw, x_bnp, os_npg(d), bias_part, dy_gain_dev,               \
+                dy_gain_div, dy_gain_coef, g.rows, g.nseg, g.nchunk);                                                         \
   } while (0)
   if (ncg == 1) SRLZ_OS_BWD(1); else SRLZ_OS_BWD(2);
 #undef SRLZ_OS_BWD
-  SRLZ_LAUNCHED();
-  hipLaunchKernelGGL(os_wgrad_reduce, dim3(ncg * 64 * 48 / 64), dim3(1024), 0, st, partial, g.grid, d->c, dw_ref);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(os_wgrad_reduce, dim3(ncg * 64 * 48 / 64), dim3(1024), 0, st, partial, g.grid, d->c, dw_ref);
   if (dbias) {
-    hipLaunchKernelGGL(os_chan_sum_final, dim3(d->c), dim3(64), 0, st, bias_part, g.grid, dbias);
-    SRLZ_LAUNCHED();
+    SRLZ_LAUNCH(os_chan_sum_final, dim3(d->c), dim3(64), 0, st, bias_part, g.grid, dbias);
   }
   return 0;
 }

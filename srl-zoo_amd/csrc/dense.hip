@@ -249,9 +249,8 @@ inline int rchunk_for(int tiles, int R) {
 
 template <bool A_RC, bool B_RC, bool A_U8, bool B_U8, int EPI, bool T_U8>
 int launch_tile(const TileArgs& a, int z, hipStream_t st) {
-  hipLaunchKernelGGL((dense_tile_kernel<A_RC, B_RC, A_U8, B_U8, EPI, T_U8>), dim3(cdiv(a.J + (a.ones_col >= 0 ? 1 : 0), 64), cdiv(a.I, 64), z),
-                     dim3(256), 0, st, a);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH((dense_tile_kernel<A_RC, B_RC, A_U8, B_U8, EPI, T_U8>), dim3(cdiv(a.J + (a.ones_col >= 0 ? 1 : 0), 64), cdiv(a.I, 64), z),
+              dim3(256), 0, st, a);
   return 0;
 }
 
@@ -305,8 +304,7 @@ extern "C" int srlz_dense_in_fwd(const float* x, const uint8_t* x_u8, const floa
   const int e = x ? launch_tile<true, true, false, false, EPI_PART, false>(a, Z, st)
                   : launch_tile<true, true, true, false, EPI_PART, false>(a, Z, st);
   if (e) return e;
-  hipLaunchKernelGGL(splitk_sum_kernel, dim3(cdiv((long long)M * n, 256)), dim3(256), 0, st, (const float*)ws, Z, M, n, b, act, y);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(splitk_sum_kernel, dim3(cdiv((long long)M * n, 256)), dim3(256), 0, st, (const float*)ws, Z, M, n, b, act, y);
   return 0;
 }
 
@@ -323,8 +321,7 @@ extern "C" int srlz_dense_in_wgrad(const float* dy, const float* x, const uint8_
                   : launch_tile<false, false, false, true, EPI_STORE, false>(a, 1, st);
   if (e) return e;
   if (db) {
-    hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, dy, M, n, db);
-    SRLZ_LAUNCHED();
+    SRLZ_LAUNCH(colsum_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, dy, M, n, db);
   }
   return 0;
 }
@@ -384,9 +381,8 @@ int out_grads(const float* dout, const float* z, const float* w, float* dz, floa
     d.I = M; d.J = n; d.R = K; d.rchunk = rc; d.C = part;
     e = launch_tile<true, false, false, false, EPI_PART, false>(d, Z, st);
     if (e) return e;
-    hipLaunchKernelGGL(splitk_sum_kernel, dim3(cdiv((long long)M * n, 256)), dim3(256), 0, st, (const float*)part, Z, M, n,
-                       (const float*)nullptr, 0, dz);
-    SRLZ_LAUNCHED();
+    SRLZ_LAUNCH(splitk_sum_kernel, dim3(cdiv((long long)M * n, 256)), dim3(256), 0, st, (const float*)part, Z, M, n, (const float*)nullptr,
+                0, dz);
   }
   return 0;
 }
@@ -429,23 +425,20 @@ extern "C" int srlz_dense_out_bwd_from(const float* dout, const float* z, const 
 extern "C" int srlz_tanh_fwd(const float* x, float* y, int n, srlz_stream_t stream) {
   SRLZ_REQUIRE(x && y, SRLZ_ERR_NULL, "tanh_fwd: null pointer");
   SRLZ_REQUIRE(n >= 1, SRLZ_ERR_BAD_DESC, "tanh_fwd: n = %d", n);
-  hipLaunchKernelGGL(tanh_fwd_kernel, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), x, y, n);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(tanh_fwd_kernel, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), x, y, n);
   return 0;
 }
 
 extern "C" int srlz_tanh_bwd(const float* y, const float* dy, float* dx, int n, srlz_stream_t stream) {
   SRLZ_REQUIRE(y && dy && dx, SRLZ_ERR_NULL, "tanh_bwd: null pointer");
   SRLZ_REQUIRE(n >= 1, SRLZ_ERR_BAD_DESC, "tanh_bwd: n = %d", n);
-  hipLaunchKernelGGL(tanh_bwd_kernel, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), y, dy, dx, n);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(tanh_bwd_kernel, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), y, dy, dx, n);
   return 0;
 }
 
 extern "C" int srlz_add_f32(const float* a, const float* b, float* out, int n, srlz_stream_t stream) {
   SRLZ_REQUIRE(a && b && out, SRLZ_ERR_NULL, "add_f32: null pointer");
   SRLZ_REQUIRE(n >= 1, SRLZ_ERR_BAD_DESC, "add_f32: n = %d", n);
-  hipLaunchKernelGGL(add_kernel, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), a, b, out, n);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(add_kernel, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), a, b, out, n);
   return 0;
 }

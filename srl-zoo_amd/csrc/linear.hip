@@ -304,20 +304,17 @@ static int launch(const float* A, long long sai, long long sar, const float* B, 
   const float* kres = nz > 1 ? nullptr : res;
   if (vec) {
 #define SRLZ_VEC_LAUNCH(AIV, BIV) \
-    hipLaunchKernelGGL((gemm_vec_kernel<AIV, BIV>), grid, dim3(256), 0, st, A, lda, B, ldb, kbias, kC, I, J, R, krelu, rchunk, kres, ldr)
+    SRLZ_LAUNCH((gemm_vec_kernel<AIV, BIV>), grid, dim3(256), 0, st, A, lda, B, ldb, kbias, kC, I, J, R, krelu, rchunk, kres, ldr)
     if (ai && bi) SRLZ_VEC_LAUNCH(true, true);
     else if (ai) SRLZ_VEC_LAUNCH(true, false);
     else if (bi) SRLZ_VEC_LAUNCH(false, true);
     else SRLZ_VEC_LAUNCH(false, false);
 #undef SRLZ_VEC_LAUNCH
   } else {
-    hipLaunchKernelGGL(gemm_strided_kernel, grid, dim3(256), 0, st, A, sai, sar, B, sbr, sbj, kbias, kC, I, J, R, krelu, rchunk, kres, ldr);
+    SRLZ_LAUNCH(gemm_strided_kernel, grid, dim3(256), 0, st, A, sai, sar, B, sbr, sbj, kbias, kC, I, J, R, krelu, rchunk, kres, ldr);
   }
-  SRLZ_LAUNCHED();
   if (nz > 1) {
-    hipLaunchKernelGGL(splitk_combine_kernel, dim3((I * J + 255) / 256), dim3(256), 0, st, (const float*)ws, nz, bias, C, I, J,
-                       relu, res, ldr);
-    SRLZ_LAUNCHED();
+    SRLZ_LAUNCH(splitk_combine_kernel, dim3((I * J + 255) / 256), dim3(256), 0, st, (const float*)ws, nz, bias, C, I, J, relu, res, ldr);
   }
   return 0;
 }
@@ -363,8 +360,7 @@ extern "C" int srlz_linear_bwd_weight(const float* dy, const float* x, float* dw
   SRLZ_REQUIRE(dy && x && dw, SRLZ_ERR_NULL, "linear_bwd_weight: null pointer");
   if (int rc = launch(dy, 1, N, x, K, 1, nullptr, dw, N, K, M, 0, ws, ws_bytes, as_stream(stream))) return rc;
   if (db) {
-    hipLaunchKernelGGL(colsum_kernel, dim3((N + 63) / 64), dim3(256), 0, as_stream(stream), dy, db, M, N);
-    SRLZ_LAUNCHED();
+    SRLZ_LAUNCH(colsum_kernel, dim3((N + 63) / 64), dim3(256), 0, as_stream(stream), dy, db, M, N);
   }
   return 0;
 }
@@ -374,7 +370,6 @@ extern "C" int srlz_relu_bwd_inplace(const float* y, float* dy, long long n, srl
   long long blocks = (n + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(relu_bwd_kernel, dim3((int)blocks), dim3(256), 0, as_stream(stream), y, dy, n);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(relu_bwd_kernel, dim3((int)blocks), dim3(256), 0, as_stream(stream), y, dy, n);
   return 0;
 }

@@ -17,31 +17,22 @@ __global__ __launch_bounds__(256) void reduce_partial(const float* __restrict__ 
   b += (size_t)blockIdx.y * n;
   partial += (size_t)blockIdx.y * gridDim.x;
   double acc = 0.0;
-  const long long n4 = n >> 2;
-  const long long stride = (long long)gridDim.x * blockDim.x;
   float local = 0.f;
   int cnt = 0;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+  const auto term = [&](float x, float y) {
+    if (OP == 0) { const float d = x - y; local += d * d; }
+    else local += -0.5f * (1.f + y - x * x - expf(y));
+  };
+  for_each_quad(n, [&](long long i) {
     const f32x4 x = *(const f32x4*)(a + i * 4);
     const f32x4 y = *(const f32x4*)(b + i * 4);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (OP == 0) { const float d = x[j] - y[j]; local += d * d; }
-      else local += -0.5f * (1.f + y[j] - x[j] * x[j] - expf(y[j]));
-    }
+    for (int j = 0; j < 4; ++j) term(x[j], y[j]);
     if (++cnt == 8) { acc += (double)local; local = 0.f; cnt = 0; }
-  }
-  // tail
-  for (long long i = n4 * 4 + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    if (OP == 0) { const float d = a[i] - b[i]; local += d * d; }
-    else local += -0.5f * (1.f + b[i] - a[i] * a[i] - expf(b[i]));
-  }
+  }, [&](long long i) { term(a[i], b[i]); });
   acc += (double)local;
-  acc = wave_sum_d(acc);
-  __shared__ double sm[4];
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = sm[0] + sm[1] + sm[2] + sm[3];
+  const double total = block_sum_d(acc);
+  if (threadIdx.x == 0) partial[blockIdx.x] = total;
 }
 
 __global__ void reduce_final(const double* __restrict__ partial, int nb, float* __restrict__ out, float div) {
@@ -61,17 +52,14 @@ __global__ __launch_bounds__(256) void sqdiff_grad_kernel(const float* __restric
   // shared scalar); g = (upstream / div) * coef in exactly that order — what autograd computes for sum(..)/numel
   a += (size_t)blockIdx.y * n; b += (size_t)blockIdx.y * n; da += (size_t)blockIdx.y * n;
   const float g = ((coef_dev ? coef_dev[blockIdx.y * coef_stride] : 1.f) / div) * coef;
-  const long long n4 = n >> 2;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+  for_each_quad(n, [&](long long i) {
     const f32x4 x = *(const f32x4*)(a + i * 4);
     const f32x4 y = *(const f32x4*)(b + i * 4);
     f32x4 o;
 #pragma unroll
     for (int j = 0; j < 4; ++j) o[j] = g * (x[j] - y[j]);
     *(f32x4*)(da + i * 4) = o;
-  }
-  for (long long i = n4 * 4 + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) da[i] = g * (a[i] - b[i]);
+  }, [&](long long i) { da[i] = g * (a[i] - b[i]); });
 }
 
 __global__ void kl_grad_kernel(const float* __restrict__ mu, const float* __restrict__ lv, const float* __restrict__ coef_dev,
@@ -83,14 +71,15 @@ __global__ void kl_grad_kernel(const float* __restrict__ mu, const float* __rest
   }
 }
 
-__global__ void reparam_fwd_kernel(const float* __restrict__ mu, const float* __restrict__ lv, const float* __restrict__ eps,
-                                   float* __restrict__ z, long long n) {
+__global__ __launch_bounds__(256) void reparam_fwd_kernel(const float* __restrict__ mu, const float* __restrict__ lv,
+                                                         const float* __restrict__ eps, float* __restrict__ z, long long n) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
     z[i] = eps[i] * expf(0.5f * lv[i]) + mu[i];
 }
 
-__global__ void reparam_bwd_kernel(const float* __restrict__ dz, const float* __restrict__ lv, const float* __restrict__ eps,
-                                   float* __restrict__ dmu, float* __restrict__ dlv, long long n) {
+__global__ __launch_bounds__(256) void reparam_bwd_kernel(const float* __restrict__ dz, const float* __restrict__ lv,
+                                                         const float* __restrict__ eps, float* __restrict__ dmu,
+                                                         float* __restrict__ dlv, long long n) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     dmu[i] = dz[i];
     dlv[i] = dz[i] * eps[i] * 0.5f * expf(0.5f * lv[i]);
@@ -98,8 +87,8 @@ __global__ void reparam_bwd_kernel(const float* __restrict__ dz, const float* __
 }
 
 // one block; thread per sample
-__global__ void cross_entropy_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target, int B, int A,
-                                     float* __restrict__ out, float* __restrict__ dlogits) {
+__global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
+                                                           int B, int A, float* __restrict__ out, float* __restrict__ dlogits) {
   double acc = 0.0;
   for (int b = threadIdx.x; b < B; b += blockDim.x) {
     const float* l = logits + (size_t)b * A;
@@ -115,11 +104,8 @@ __global__ void cross_entropy_kernel(const float* __restrict__ logits, const int
       for (int j = 0; j < A; ++j) dlogits[(size_t)b * A + j] = (expf(l[j] - lse) - (j == t ? 1.f : 0.f)) * invB;
     }
   }
-  acc = wave_sum_d(acc);
-  __shared__ double sm[4];
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) out[0] = (float)((sm[0] + sm[1] + sm[2] + sm[3]) / (double)B);
+  const double total = block_sum_d(acc);
+  if (threadIdx.x == 0) out[0] = (float)(total / (double)B);
 }
 
 __global__ void concat_onehot_kernel(const float* __restrict__ s, const int64_t* __restrict__ a, float* __restrict__ cat,
@@ -131,21 +117,26 @@ __global__ void concat_onehot_kernel(const float* __restrict__ s, const int64_t*
   }
 }
 
+// torch.optim.Adam (no amsgrad, no weight decay): m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ;
+// p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
+// Every scalar is evaluated in DOUBLE on the host and rounded once, as torch does with its Python floats
+// (step_size = lr / (1 - b1^t), omb = 1 - beta): 1.f - 0.999f would be 0.00099998713, 1.3e-5 away from torch's 0.001f.
+// One element's update, the ONE body of the host-step and the device-step kernel: the two must agree bit for bit.
+__device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, float step_size, float b1, float b2, float eps,
+                                            float omb1, float omb2, float bc2_sqrt, float grad_scale) {
+  const float gi = g * grad_scale;
+  const float mi = b1 * m + omb1 * gi;
+  const float vi = b2 * v + omb2 * gi * gi;
+  m = mi; v = vi;
+  const float denom = sqrtf(vi) / bc2_sqrt + eps;
+  p -= step_size * (mi / denom);
+}
+
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                   float* __restrict__ v, long long n, float step_size, float b1, float b2,
                                                   float eps, float omb1, float omb2, float bc2_sqrt, float grad_scale) {
-  // torch.optim.Adam (no amsgrad, no weight decay): m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ;
-  // p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
-  // Every scalar is evaluated in DOUBLE on the host and rounded once, as torch does with its Python floats
-  // (step_size = lr / (1 - b1^t), omb = 1 - beta): 1.f - 0.999f would be 0.00099998713, 1.3e-5 away from torch's 0.001f.
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const float gi = g[i] * grad_scale;
-    const float mi = b1 * m[i] + omb1 * gi;
-    const float vi = b2 * v[i] + omb2 * gi * gi;
-    m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] -= step_size * (mi / denom);
-  }
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+    adam_update(p[i], g[i], m[i], v[i], step_size, b1, b2, eps, omb1, omb2, bc2_sqrt, grad_scale);
 }
 
 // y[r][c] = x[r][c] for lo <= c < hi, 0 elsewhere (SRLModulesSplit.detachSplit, models/modules.py:191-236: the state is
@@ -174,14 +165,8 @@ __global__ __launch_bounds__(256) void param_norms_kernel(const float* const* __
     }
     acc += (double)local;
   }
-  acc = wave_sum_d(acc);
-  __shared__ double sm[4];
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const double t = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-    norms[blockIdx.x] = (float)(mode == 0 ? t : sqrt(t));
-  }
+  const double t = block_sum_pairs_d(acc);
+  if (threadIdx.x == 0) norms[blockIdx.x] = (float)(mode == 0 ? t : sqrt(t));
 }
 
 // out = scale * sum_i norms[i]   (one wave; fp64)
@@ -239,23 +224,16 @@ __global__ void adam_tick_kernel(int* __restrict__ step_dev, float* __restrict__
 }
 
 __global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                      float* __restrict__ v, long long n, float b1, float b2,
-                                                      float eps, float omb1, float omb2, const float* __restrict__ bc,
-                                                      float grad_scale) {
-  const float step_size = bc[0];
-  const float bc2_sqrt = bc[1];
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const float gi = g[i] * grad_scale;
-    const float mi = b1 * m[i] + omb1 * gi;
-    const float vi = b2 * v[i] + omb2 * gi * gi;
-    m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] -= step_size * (mi / denom);
-  }
+                                                      float* __restrict__ v, long long n, float b1, float b2, float eps, float omb1,
+                                                      float omb2, const float* __restrict__ bc, float grad_scale) {
+  const float step_size = bc[0], bc2_sqrt = bc[1];
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+    adam_update(p[i], g[i], m[i], v[i], step_size, b1, b2, eps, omb1, omb2, bc2_sqrt, grad_scale);
 }
 
 // nn.PReLU() (one slope, init 0.25) — EmbeddingNet.fc[0], /root/reference/models/triplet.py:24
-__global__ void prelu_fwd_kernel(const float* __restrict__ x, const float* __restrict__ slope, float* __restrict__ y, long long n) {
+__global__ __launch_bounds__(256) void prelu_fwd_kernel(const float* __restrict__ x, const float* __restrict__ slope,
+                                                       float* __restrict__ y, long long n) {
   const float a = slope[0];
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
     y[i] = x[i] > 0.f ? x[i] : a * x[i];
@@ -272,11 +250,8 @@ __global__ __launch_bounds__(256) void prelu_bwd_kernel(const float* __restrict_
     dx[i] = xi > 0.f ? g : a * g;
     if (!(xi > 0.f)) acc += (double)(g * xi);
   }
-  acc = wave_sum_d(acc);
-  __shared__ double sm[4];
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) dslope[0] = (float)(sm[0] + sm[1] + sm[2] + sm[3]);
+  const double total = block_sum_d(acc);
+  if (threadIdx.x == 0) dslope[0] = (float)total;
 }
 
 // tripletLoss, /root/reference/losses/losses.py:360-376: mean_b relu(|s-p|^2 - |s-n|^2 + alpha).  One block; hinge[b] keeps
@@ -296,11 +271,8 @@ __global__ __launch_bounds__(256) void triplet_fwd_kernel(const float* __restric
     hinge[b] = l > 0.f ? 1.f : 0.f;
     acc += (double)(l > 0.f ? l : 0.f);
   }
-  acc = wave_sum_d(acc);
-  __shared__ double sm[4];
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) out[0] = (float)((sm[0] + sm[1] + sm[2] + sm[3]) / (double)B);
+  const double total = block_sum_d(acc);
+  if (threadIdx.x == 0) out[0] = (float)(total / (double)B);
 }
 
 // d/ds = g/B * hinge * 2 (n - p) ; d/dp = -g/B * hinge * 2 (s - p) ; d/dn = g/B * hinge * 2 (s - n)
@@ -336,10 +308,8 @@ static int reduce_launch(const float* a, const float* b, long long n, int groups
   SRLZ_REQUIRE(((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0 && (groups == 1 || (n & 3) == 0), SRLZ_ERR_BAD_DESC,
                "reduce: inputs (and every group's slice) must be 16-byte aligned");
   const int nb = blocks_for((n + 3) / 4, RED_BLOCKS);
-  hipLaunchKernelGGL(reduce_partial<OP>, dim3(nb, groups), dim3(256), 0, st, a, b, n, (double*)ws);
-  SRLZ_LAUNCHED();
-  hipLaunchKernelGGL(reduce_final, dim3(groups), dim3(64), 0, st, (const double*)ws, nb, out, div);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(reduce_partial<OP>, dim3(nb, groups), dim3(256), 0, st, a, b, n, (double*)ws);
+  SRLZ_LAUNCH(reduce_final, dim3(groups), dim3(64), 0, st, (const double*)ws, nb, out, div);
   return 0;
 }
 
@@ -363,10 +333,7 @@ __global__ __launch_bounds__(256) void join2_kernel(const float* __restrict__ a,
                                                    float* __restrict__ out, long long n) {
   const float* __restrict__ src = blockIdx.y ? b : a;
   float* __restrict__ dst = out + (size_t)blockIdx.y * n;
-  const long long n4 = n >> 2, stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride)
-    *(f32x4*)(dst + i * 4) = *(const f32x4*)(src + i * 4);
-  for (long long i = n4 * 4 + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) dst[i] = src[i];
+  for_each_quad(n, [&](long long i) { *(f32x4*)(dst + i * 4) = *(const f32x4*)(src + i * 4); }, [&](long long i) { dst[i] = src[i]; });
 }
 
 // cat([a, b], dim 1) of two row-major matrices with the same number of rows (inverse / reward heads: [state ; next_state],
@@ -436,8 +403,7 @@ extern "C" int srlz_weighted_total(const float* const* scalars, const float* wei
     L.p[i] = scalars[i]; L.w[i] = weights[i];
   }
   L.n = n;
-  hipLaunchKernelGGL(weighted_total_kernel, dim3(1), dim3(64), 0, as_stream(stream), L, total, tail);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(weighted_total_kernel, dim3(1), dim3(64), 0, as_stream(stream), L, total, tail);
   return 0;
 }
 
@@ -447,26 +413,23 @@ extern "C" int srlz_weighted_total_bwd(const float* dout, const float* weights, 
   ScalarList L;
   for (int i = 0; i < n; ++i) { L.p[i] = nullptr; L.w[i] = weights[i]; }
   L.n = n;
-  hipLaunchKernelGGL(weighted_total_bwd_kernel, dim3(1), dim3(64), 0, as_stream(stream), L, dout, g);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(weighted_total_bwd_kernel, dim3(1), dim3(64), 0, as_stream(stream), L, dout, g);
   return 0;
 }
 
 extern "C" int srlz_cat_cols(const float* a, const float* b, float* out, int rows, int ca, int cb, srlz_stream_t stream) {
   SRLZ_REQUIRE(a && b && out, SRLZ_ERR_NULL, "cat_cols: null pointer");
   SRLZ_REQUIRE(rows > 0 && ca > 0 && cb > 0, SRLZ_ERR_BAD_DESC, "cat_cols: %d rows of %d + %d columns", rows, ca, cb);
-  hipLaunchKernelGGL(cat_cols_kernel, dim3(blocks_for((long long)rows * (ca + cb), 1024)), dim3(256), 0, as_stream(stream), a, b, out,
-                     rows, ca, cb);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(cat_cols_kernel, dim3(blocks_for((long long)rows * (ca + cb), 1024)), dim3(256), 0, as_stream(stream), a, b, out, rows, ca,
+              cb);
   return 0;
 }
 
 extern "C" int srlz_split_cols(const float* in, float* a, float* b, int rows, int ca, int cb, srlz_stream_t stream) {
   SRLZ_REQUIRE(in && (a || b), SRLZ_ERR_NULL, "split_cols: null pointer");
   SRLZ_REQUIRE(rows > 0 && ca > 0 && cb > 0, SRLZ_ERR_BAD_DESC, "split_cols: %d rows of %d + %d columns", rows, ca, cb);
-  hipLaunchKernelGGL(split_cols_kernel, dim3(blocks_for((long long)rows * (ca + cb), 1024)), dim3(256), 0, as_stream(stream), in, a, b,
-                     rows, ca, cb);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(split_cols_kernel, dim3(blocks_for((long long)rows * (ca + cb), 1024)), dim3(256), 0, as_stream(stream), in, a, b, rows, ca,
+              cb);
   return 0;
 }
 
@@ -480,8 +443,7 @@ extern "C" int srlz_sum_terms(const float* const* terms, int nterms, float* out,
     L.p[i] = terms[i];
   }
   L.n = nterms;
-  hipLaunchKernelGGL(sum_terms_kernel, dim3(blocks_for(n, 1024)), dim3(256), 0, as_stream(stream), L, out, n);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(sum_terms_kernel, dim3(blocks_for(n, 1024)), dim3(256), 0, as_stream(stream), L, out, n);
   return 0;
 }
 
@@ -509,9 +471,8 @@ extern "C" int srlz_sqdiff_sum_groups(const float* a, const float* b, long long 
 extern "C" int srlz_sqdiff_grad(const float* a, const float* b, const float* coef_dev, float coef, float* da, long long n,
                                 srlz_stream_t stream) {
   SRLZ_REQUIRE(a && b && da, SRLZ_ERR_NULL, "sqdiff_grad: null pointer");
-  hipLaunchKernelGGL(sqdiff_grad_kernel, dim3(blocks_for((n + 3) / 4, 8192)), dim3(256), 0, as_stream(stream), a, b, coef_dev,
-                     coef, da, n, 0, 1.0f);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(sqdiff_grad_kernel, dim3(blocks_for((n + 3) / 4, 8192)), dim3(256), 0, as_stream(stream), a, b, coef_dev, coef, da, n, 0,
+              1.0f);
   return 0;
 }
 
@@ -521,9 +482,8 @@ extern "C" int srlz_sqdiff_grad_groups(const float* a, const float* b, const flo
   SRLZ_REQUIRE(groups >= 1 && groups <= MAX_GROUPS && (groups == 1 || (n_per_group & 3) == 0) && div != 0.f &&
                (coef_stride == 0 || coef_stride == 1), SRLZ_ERR_BAD_DESC,
                "sqdiff_grad_groups: groups = %d, %lld elements each", groups, n_per_group);
-  hipLaunchKernelGGL(sqdiff_grad_kernel, dim3(blocks_for((n_per_group + 3) / 4, 8192 / groups), groups), dim3(256), 0,
-                     as_stream(stream), a, b, coef_dev, coef, da, n_per_group, coef_stride, div);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(sqdiff_grad_kernel, dim3(blocks_for((n_per_group + 3) / 4, 8192 / groups), groups), dim3(256), 0, as_stream(stream), a, b,
+              coef_dev, coef, da, n_per_group, coef_stride, div);
   return 0;
 }
 
@@ -535,10 +495,8 @@ extern "C" int srlz_sqdiff_pair_loss(const float* a, const float* b, long long n
                "sqdiff_pair_loss: halves must be 16-byte aligned multiples of 4 floats");
   hipStream_t st = as_stream(stream);
   const int nb = blocks_for((n_per_group + 3) / 4, RED_BLOCKS);  // per group the geometry of a single-group srlz_sqdiff_sum
-  hipLaunchKernelGGL(reduce_partial<0>, dim3(nb, 2), dim3(256), 0, st, a, b, n_per_group, (double*)ws);
-  SRLZ_LAUNCHED();
-  hipLaunchKernelGGL(pair_loss_final, dim3(1), dim3(128), 0, st, (const double*)ws, nb, sums, comb, (float)n_per_group, mean);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(reduce_partial<0>, dim3(nb, 2), dim3(256), 0, st, a, b, n_per_group, (double*)ws);
+  SRLZ_LAUNCH(pair_loss_final, dim3(1), dim3(128), 0, st, (const double*)ws, nb, sums, comb, (float)n_per_group, mean);
   return 0;
 }
 
@@ -549,8 +507,7 @@ extern "C" int srlz_pair_loss_finalize(const double* partial, int nb, long long 
                                        srlz_stream_t stream) {
   SRLZ_REQUIRE(partial && sums && comb, SRLZ_ERR_NULL, "pair_loss_finalize: null pointer");
   SRLZ_REQUIRE(nb > 0 && n_per_group > 0, SRLZ_ERR_BAD_DESC, "pair_loss_finalize: nb = %d, n = %lld", nb, n_per_group);
-  hipLaunchKernelGGL(pair_loss_final, dim3(1), dim3(128), 0, as_stream(stream), partial, nb, sums, comb, (float)n_per_group, mean);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(pair_loss_final, dim3(1), dim3(128), 0, as_stream(stream), partial, nb, sums, comb, (float)n_per_group, mean);
   return 0;
 }
 
@@ -560,15 +517,12 @@ namespace {
 __global__ __launch_bounds__(256) void scale_by_scalar_kernel(const float* __restrict__ x, const float* __restrict__ gain_dev, float div,
                                                              float coef, float* __restrict__ out, long long n) {
   const float g = (gain_dev[0] / div) * coef;
-  const long long n4 = n >> 2;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+  for_each_quad(n, [&](long long i) {
     f32x4 v = *(const f32x4*)(x + i * 4);
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] *= g;
     *(f32x4*)(out + i * 4) = v;
-  }
-  for (long long i = n4 * 4 + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = g * x[i];
+  }, [&](long long i) { out[i] = g * x[i]; });
 }
 }  // namespace
 
@@ -577,9 +531,8 @@ extern "C" int srlz_scale_by_scalar(const float* x, const float* gain_dev, float
   SRLZ_REQUIRE(x && gain_dev && out, SRLZ_ERR_NULL, "scale_by_scalar: null pointer");
   SRLZ_REQUIRE(div != 0.f && ((uintptr_t)x & 15) == 0 && ((uintptr_t)out & 15) == 0, SRLZ_ERR_BAD_DESC,
                "scale_by_scalar: zero divisor or unaligned buffers");
-  hipLaunchKernelGGL(scale_by_scalar_kernel, dim3(blocks_for((n + 3) / 4, 8192)), dim3(256), 0, as_stream(stream), x, gain_dev, div,
-                     coef, out, n);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(scale_by_scalar_kernel, dim3(blocks_for((n + 3) / 4, 8192)), dim3(256), 0, as_stream(stream), x, gain_dev, div, coef, out,
+              n);
   return 0;
 }
 
@@ -587,8 +540,7 @@ extern "C" int srlz_join2(const float* a, const float* b, float* out, long long 
   SRLZ_REQUIRE(a && b && out, SRLZ_ERR_NULL, "join2: null pointer");
   SRLZ_REQUIRE(n_each > 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 15) == 0 && (n_each & 3) == 0, SRLZ_ERR_BAD_DESC,
                "join2: halves must be 16-byte aligned multiples of 4 floats (%lld)", n_each);
-  hipLaunchKernelGGL(join2_kernel, dim3(blocks_for((n_each + 3) / 4, 4096), 2), dim3(256), 0, as_stream(stream), a, b, out, n_each);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(join2_kernel, dim3(blocks_for((n_each + 3) / 4, 4096), 2), dim3(256), 0, as_stream(stream), a, b, out, n_each);
   return 0;
 }
 
@@ -600,41 +552,34 @@ extern "C" int srlz_kl_sum(const float* mu, const float* logvar, long long n, fl
 extern "C" int srlz_kl_grad(const float* mu, const float* logvar, const float* coef_dev, float coef, float* dmu,
                             float* dlogvar, long long n, srlz_stream_t stream) {
   SRLZ_REQUIRE(mu && logvar && dmu && dlogvar, SRLZ_ERR_NULL, "kl_grad: null pointer");
-  hipLaunchKernelGGL(kl_grad_kernel, dim3(blocks_for(n, 1024)), dim3(256), 0, as_stream(stream), mu, logvar, coef_dev, coef,
-                     dmu, dlogvar, n);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(kl_grad_kernel, dim3(blocks_for(n, 1024)), dim3(256), 0, as_stream(stream), mu, logvar, coef_dev, coef, dmu, dlogvar, n);
   return 0;
 }
 
 extern "C" int srlz_reparam_fwd(const float* mu, const float* logvar, const float* eps, float* z, long long n,
                                 srlz_stream_t stream) {
   SRLZ_REQUIRE(mu && logvar && eps && z, SRLZ_ERR_NULL, "reparam_fwd: null pointer");
-  hipLaunchKernelGGL(reparam_fwd_kernel, dim3(blocks_for(n, 1024)), dim3(256), 0, as_stream(stream), mu, logvar, eps, z, n);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(reparam_fwd_kernel, dim3(blocks_for(n, 1024)), dim3(256), 0, as_stream(stream), mu, logvar, eps, z, n);
   return 0;
 }
 
 extern "C" int srlz_reparam_bwd(const float* dz, const float* logvar, const float* eps, float* dmu, float* dlogvar,
                                 long long n, srlz_stream_t stream) {
   SRLZ_REQUIRE(dz && logvar && eps && dmu && dlogvar, SRLZ_ERR_NULL, "reparam_bwd: null pointer");
-  hipLaunchKernelGGL(reparam_bwd_kernel, dim3(blocks_for(n, 1024)), dim3(256), 0, as_stream(stream), dz, logvar, eps, dmu,
-                     dlogvar, n);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(reparam_bwd_kernel, dim3(blocks_for(n, 1024)), dim3(256), 0, as_stream(stream), dz, logvar, eps, dmu, dlogvar, n);
   return 0;
 }
 
 extern "C" int srlz_prelu_fwd(const float* x, const float* slope, float* y, long long n, srlz_stream_t stream) {
   SRLZ_REQUIRE(x && slope && y, SRLZ_ERR_NULL, "prelu_fwd: null pointer");
-  hipLaunchKernelGGL(prelu_fwd_kernel, dim3(blocks_for(n, 1024)), dim3(256), 0, as_stream(stream), x, slope, y, n);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(prelu_fwd_kernel, dim3(blocks_for(n, 1024)), dim3(256), 0, as_stream(stream), x, slope, y, n);
   return 0;
 }
 
 extern "C" int srlz_prelu_bwd(const float* x, const float* slope, const float* dy, float* dx, float* dslope, long long n,
                               srlz_stream_t stream) {
   SRLZ_REQUIRE(x && slope && dy && dx && dslope, SRLZ_ERR_NULL, "prelu_bwd: null pointer");
-  hipLaunchKernelGGL(prelu_bwd_kernel, dim3(1), dim3(256), 0, as_stream(stream), x, slope, dy, dx, dslope, n);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(prelu_bwd_kernel, dim3(1), dim3(256), 0, as_stream(stream), x, slope, dy, dx, dslope, n);
   return 0;
 }
 
@@ -642,17 +587,15 @@ extern "C" int srlz_triplet_fwd(const float* s, const float* p, const float* n, 
                                 float* hinge, srlz_stream_t stream) {
   SRLZ_REQUIRE(s && p && n && out && hinge, SRLZ_ERR_NULL, "triplet_fwd: null pointer");
   SRLZ_REQUIRE(B > 0 && S > 0, SRLZ_ERR_BAD_DESC, "triplet_fwd: empty batch");
-  hipLaunchKernelGGL(triplet_fwd_kernel, dim3(1), dim3(256), 0, as_stream(stream), s, p, n, B, S, alpha, out, hinge);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(triplet_fwd_kernel, dim3(1), dim3(256), 0, as_stream(stream), s, p, n, B, S, alpha, out, hinge);
   return 0;
 }
 
 extern "C" int srlz_triplet_bwd(const float* s, const float* p, const float* n, const float* hinge, const float* g, int B, int S,
                                 float* ds, float* dp, float* dn, srlz_stream_t stream) {
   SRLZ_REQUIRE(s && p && n && hinge && g && ds && dp && dn, SRLZ_ERR_NULL, "triplet_bwd: null pointer");
-  hipLaunchKernelGGL(triplet_bwd_kernel, dim3(blocks_for((long long)B * S, 1024)), dim3(256), 0, as_stream(stream), s, p, n, hinge,
-                     g, B, S, ds, dp, dn);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(triplet_bwd_kernel, dim3(blocks_for((long long)B * S, 1024)), dim3(256), 0, as_stream(stream), s, p, n, hinge, g, B, S, ds,
+              dp, dn);
   return 0;
 }
 
@@ -660,16 +603,13 @@ extern "C" int srlz_cross_entropy(const float* logits, const int64_t* target, in
                                   srlz_stream_t stream) {
   SRLZ_REQUIRE(logits && target && out, SRLZ_ERR_NULL, "cross_entropy: null pointer");
   SRLZ_REQUIRE(B > 0 && A > 0, SRLZ_ERR_BAD_DESC, "cross_entropy: empty batch");
-  hipLaunchKernelGGL(cross_entropy_kernel, dim3(1), dim3(256), 0, as_stream(stream), logits, target, B, A, out, dlogits);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(cross_entropy_kernel, dim3(1), dim3(256), 0, as_stream(stream), logits, target, B, A, out, dlogits);
   return 0;
 }
 
 extern "C" int srlz_concat_onehot(const float* s, const int64_t* a, float* cat, int B, int S, int A, srlz_stream_t stream) {
   SRLZ_REQUIRE(s && a && cat, SRLZ_ERR_NULL, "concat_onehot: null pointer");
-  hipLaunchKernelGGL(concat_onehot_kernel, dim3(blocks_for((long long)B * (S + A), 1024)), dim3(256), 0, as_stream(stream), s, a,
-                     cat, B, S, A);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(concat_onehot_kernel, dim3(blocks_for((long long)B * (S + A), 1024)), dim3(256), 0, as_stream(stream), s, a, cat, B, S, A);
   return 0;
 }
 
@@ -677,9 +617,8 @@ extern "C" int srlz_mask_columns(const float* x, float* y, int rows, int cols, i
   SRLZ_REQUIRE(x && y, SRLZ_ERR_NULL, "mask_columns: null pointer");
   SRLZ_REQUIRE(rows > 0 && cols > 0 && lo >= 0 && lo <= hi && hi <= cols, SRLZ_ERR_BAD_DESC,
                "mask_columns: bad range [%d,%d) of %d columns", lo, hi, cols);
-  hipLaunchKernelGGL(mask_columns_kernel, dim3(blocks_for((long long)rows * cols, 1024)), dim3(256), 0, as_stream(stream), x, y,
-                     rows, cols, lo, hi);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(mask_columns_kernel, dim3(blocks_for((long long)rows * cols, 1024)), dim3(256), 0, as_stream(stream), x, y, rows, cols, lo,
+              hi);
   return 0;
 }
 
@@ -688,10 +627,8 @@ extern "C" int srlz_param_norms(const float* const* ptrs, const long long* lens,
   SRLZ_REQUIRE(ptrs && lens && norms && out, SRLZ_ERR_NULL, "param_norms: null pointer");
   SRLZ_REQUIRE(nseg > 0 && (mode == 0 || mode == 1), SRLZ_ERR_BAD_DESC, "param_norms: nseg=%d mode=%d", nseg, mode);
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(param_norms_kernel, dim3(nseg), dim3(256), 0, st, ptrs, lens, mode, norms);
-  SRLZ_LAUNCHED();
-  hipLaunchKernelGGL(param_norms_total, dim3(1), dim3(64), 0, st, (const float*)norms, nseg, scale, out);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(param_norms_kernel, dim3(nseg), dim3(256), 0, st, ptrs, lens, mode, norms);
+  SRLZ_LAUNCH(param_norms_total, dim3(1), dim3(64), 0, st, (const float*)norms, nseg, scale, out);
   return 0;
 }
 
@@ -700,9 +637,7 @@ extern "C" int srlz_param_norms_grad(const float* const* ptrs, float* const* gpt
   SRLZ_REQUIRE(ptrs && gptrs && lens && norms, SRLZ_ERR_NULL, "param_norms_grad: null pointer");
   SRLZ_REQUIRE(nseg > 0 && nseg <= 65535 && (mode == 0 || mode == 1), SRLZ_ERR_BAD_DESC, "param_norms_grad: nseg=%d mode=%d",
                nseg, mode);
-  hipLaunchKernelGGL(param_norms_grad_kernel, dim3(64, nseg), dim3(256), 0, as_stream(stream), ptrs, gptrs, lens, mode, norms,
-                     coef_dev, scale);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(param_norms_grad_kernel, dim3(64, nseg), dim3(256), 0, as_stream(stream), ptrs, gptrs, lens, mode, norms, coef_dev, scale);
   return 0;
 }
 
@@ -710,8 +645,7 @@ extern "C" int srlz_fold_grads(float* grad, float* stages, long long n, int nsta
   SRLZ_REQUIRE(grad && stages, SRLZ_ERR_NULL, "fold_grads: null pointer");
   SRLZ_REQUIRE(n > 0 && (n & 3) == 0 && nstage >= 1 && nstage <= 8, SRLZ_ERR_BAD_DESC,
                "fold_grads: n=%lld (must be a multiple of 4) nstage=%d", n, nstage);
-  hipLaunchKernelGGL(fold_grads_kernel, dim3(blocks_for(n / 4, 2048)), dim3(256), 0, as_stream(stream), grad, stages, n, nstage);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(fold_grads_kernel, dim3(blocks_for(n / 4, 2048)), dim3(256), 0, as_stream(stream), grad, stages, n, nstage);
   return 0;
 }
 
@@ -721,10 +655,8 @@ extern "C" int srlz_adam_step(float* p, const float* g, float* m, float* v, long
   SRLZ_REQUIRE(step >= 1, SRLZ_ERR_BAD_DESC, "adam_step: step is 1-based");
   const double bc1 = 1.0 - pow(beta1, (double)step);
   const double bc2 = 1.0 - pow(beta2, (double)step);
-  hipLaunchKernelGGL(adam_kernel, dim3(blocks_for(n, 2048)), dim3(256), 0, as_stream(stream), p, g, m, v, n, (float)(lr / bc1),
-                     (float)beta1, (float)beta2, (float)eps, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)sqrt(bc2),
-                     grad_scale);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(adam_kernel, dim3(blocks_for(n, 2048)), dim3(256), 0, as_stream(stream), p, g, m, v, n, (float)(lr / bc1), (float)beta1,
+              (float)beta2, (float)eps, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)sqrt(bc2), grad_scale);
   return 0;
 }
 
@@ -733,10 +665,8 @@ extern "C" int srlz_adam_step_dev(float* p, const float* g, float* m, float* v, 
                                   srlz_stream_t stream) {
   SRLZ_REQUIRE(p && g && m && v && step_dev && bc_dev, SRLZ_ERR_NULL, "adam_step_dev: null pointer");
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, st, step_dev, bc_dev, lr, beta1, beta2);
-  SRLZ_LAUNCHED();
-  hipLaunchKernelGGL(adam_dev_kernel, dim3(blocks_for(n, 2048)), dim3(256), 0, st, p, g, m, v, n, (float)beta1, (float)beta2,
-                     (float)eps, (float)(1.0 - beta1), (float)(1.0 - beta2), (const float*)bc_dev, grad_scale);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(adam_tick_kernel, dim3(1), dim3(1), 0, st, step_dev, bc_dev, lr, beta1, beta2);
+  SRLZ_LAUNCH(adam_dev_kernel, dim3(blocks_for(n, 2048)), dim3(256), 0, st, p, g, m, v, n, (float)beta1, (float)beta2, (float)eps,
+              (float)(1.0 - beta1), (float)(1.0 - beta2), (const float*)bc_dev, grad_scale);
   return 0;
 }

@@ -127,9 +127,8 @@ extern "C" int srlz_copy_frames_u8(const uint8_t* src, const long long* src_inde
   const long long words = frame_bytes / 16;
   int gx = (int)((words + 255) / 256);
   if (gx > 16) gx = 16;
-  hipLaunchKernelGGL(copy_frames_kernel, dim3(gx, n), dim3(256), 0, as_stream(stream), src, src_index, src_shift, dst, dst_index,
-                     dst_shift, words);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(copy_frames_kernel, dim3(gx, n), dim3(256), 0, as_stream(stream), src, src_index, src_shift, dst, dst_index, dst_shift,
+              words);
   return 0;
 }
 
@@ -150,9 +149,8 @@ extern "C" int srlz_copy_frames_u8_strided(const uint8_t* src, const long long* 
   const long long words = copy_bytes / 16;
   int gx = (int)((words + 255) / 256);
   if (gx > 16) gx = 16;
-  hipLaunchKernelGGL(copy_frames_strided_kernel, dim3(gx, n), dim3(256), 0, as_stream(stream), src, src_index, src_shift, src_frame_bytes / 16,
-                     src_offset_bytes / 16, dst, dst_index, dst_shift, dst_frame_bytes / 16, dst_offset_bytes / 16, words);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(copy_frames_strided_kernel, dim3(gx, n), dim3(256), 0, as_stream(stream), src, src_index, src_shift, src_frame_bytes / 16,
+              src_offset_bytes / 16, dst, dst_index, dst_shift, dst_frame_bytes / 16, dst_offset_bytes / 16, words);
   return 0;
 }
 
@@ -163,9 +161,7 @@ extern "C" int srlz_occlude_frames_u8(const uint8_t* store, const long long* ind
                "occlude_frames_u8: channels must be 3, 6 or 9 (got %d) and n * c <= 65535", c);
   int gx = (w * h + 255) / 256;
   if (gx > 64) gx = 64;
-  hipLaunchKernelGGL(occlude_frames_kernel, dim3(gx, n * c), dim3(256), 0, as_stream(stream), store, index, shift, rects, norm_lut, out,
-                     c, w, h);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(occlude_frames_kernel, dim3(gx, n * c), dim3(256), 0, as_stream(stream), store, index, shift, rects, norm_lut, out, c, w, h);
   return 0;
 }
 
@@ -175,15 +171,13 @@ extern "C" int srlz_normalize_u8(const uint8_t* img_nhwc, float* out_ncwh, int n
   SRLZ_REQUIRE(n > 0 && h > 0 && w > 0 && c > 0 && c <= 9 && c % 3 == 0, SRLZ_ERR_BAD_DESC,
                "normalize_u8: channels must be 3, 6 or 9 (got %d)", c);
   const int tiles = n * ((h + 31) / 32) * ((w + 31) / 32);
-  hipLaunchKernelGGL(normalize_u8_kernel, dim3(tiles), dim3(256), 0, as_stream(stream), img_nhwc, out_ncwh, n, h, w, c);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(normalize_u8_kernel, dim3(tiles), dim3(256), 0, as_stream(stream), img_nhwc, out_ncwh, n, h, w, c);
   return 0;
 }
 
 extern "C" int srlz_normalize_lut(float* lut, srlz_stream_t stream) {
   SRLZ_REQUIRE(lut, SRLZ_ERR_NULL, "normalize_lut: null pointer");
-  hipLaunchKernelGGL(normalize_lut_kernel, dim3(3), dim3(256), 0, as_stream(stream), lut);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(normalize_lut_kernel, dim3(3), dim3(256), 0, as_stream(stream), lut);
   return 0;
 }
 
@@ -194,7 +188,6 @@ extern "C" int srlz_normalize_u8_planar(const uint8_t* x_u8, const float* norm_l
                "normalize_u8_planar: channels must be 3, 6 or 9 (got %d) and n * c <= 65535", c);
   int gx = (int)((plane + 255) / 256);
   if (gx > 64) gx = 64;
-  hipLaunchKernelGGL(normalize_u8_planar_kernel, dim3(gx, n * c), dim3(256), 0, as_stream(stream), x_u8, norm_lut, out, c, plane);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(normalize_u8_planar_kernel, dim3(gx, n * c), dim3(256), 0, as_stream(stream), x_u8, norm_lut, out, c, plane);
   return 0;
 }

@@ -374,8 +374,7 @@ extern "C" int srlz_reward_prior_fwd(const float* states, const float* rewards, 
   SRLZ_REQUIRE(B >= 2 && S >= 1, SRLZ_ERR_BAD_DESC, "reward_prior_fwd: needs B >= 2 rows and S >= 1 columns (B=%d, S=%d)", B, S);
   SRLZ_REQUIRE(ws_bytes >= srlz_reward_prior_workspace(S), SRLZ_ERR_WORKSPACE, "reward_prior_fwd: workspace %zu < %zu bytes",
                ws_bytes, srlz_reward_prior_workspace(S));
-  hipLaunchKernelGGL(reward_prior_fwd_kernel, dim3(1), dim3(RP_THREADS), 0, as_stream(stream), states, rewards, B, S, out, ws);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(reward_prior_fwd_kernel, dim3(1), dim3(RP_THREADS), 0, as_stream(stream), states, rewards, B, S, out, ws);
   return 0;
 }
 
@@ -386,9 +385,8 @@ extern "C" int srlz_reward_prior_bwd(const float* states, const float* rewards, 
   SRLZ_REQUIRE(ws_bytes >= srlz_reward_prior_workspace(S), SRLZ_ERR_WORKSPACE, "reward_prior_bwd: workspace %zu < %zu bytes",
                ws_bytes, srlz_reward_prior_workspace(S));
   const long long n = (long long)B * S;
-  hipLaunchKernelGGL(reward_prior_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), states, rewards,
-                     ws, g, B, S, dstates);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(reward_prior_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), states, rewards, ws, g, B, S,
+              dstates);
   return 0;
 }
 
@@ -404,10 +402,8 @@ extern "C" int srlz_episode_prior_fwd(const float* states, const int* others, co
   const EpLayout L = ep_layout(B, S);
   SRLZ_REQUIRE(ws_bytes >= L.total, SRLZ_ERR_WORKSPACE, "episode_prior_fwd: workspace %zu < %zu bytes", ws_bytes, L.total);
   const int grid = (B + EP_ROWS - 1) / EP_ROWS;
-  hipLaunchKernelGGL(episode_prior_fwd_kernel, dim3(grid), dim3(256), 0, as_stream(stream), states, others, same, B, S, w1, b1, w2,
-                     b2, w3, b3, at<float>(ws, L.h1), at<float>(ws, L.h2), at<float>(ws, L.p), at<double>(ws, L.rowloss), out,
-                     ticket);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(episode_prior_fwd_kernel, dim3(grid), dim3(256), 0, as_stream(stream), states, others, same, B, S, w1, b1, w2, b2, w3, b3,
+              at<float>(ws, L.h1), at<float>(ws, L.h2), at<float>(ws, L.p), at<double>(ws, L.rowloss), out, ticket);
   return 0;
 }
 
@@ -421,14 +417,12 @@ extern "C" int srlz_episode_prior_bwd(const float* states, const int* others, co
                B, S);
   const EpLayout L = ep_layout(B, S);
   SRLZ_REQUIRE(ws_bytes >= L.total, SRLZ_ERR_WORKSPACE, "episode_prior_bwd: workspace %zu < %zu bytes", ws_bytes, L.total);
-  hipLaunchKernelGGL(episode_prior_bwd_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, as_stream(stream), same, g, B, S, w1, w2, w3,
-                     at<float>(ws, L.h1), at<float>(ws, L.h2), at<float>(ws, L.p), at<float>(ws, L.dz), at<float>(ws, L.dh1),
-                     at<float>(ws, L.dh2), at<float>(ws, L.dx));
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(episode_prior_bwd_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, as_stream(stream), same, g, B, S, w1, w2, w3,
+              at<float>(ws, L.h1), at<float>(ws, L.h2), at<float>(ws, L.p), at<float>(ws, L.dz), at<float>(ws, L.dh1), at<float>(ws, L.dh2),
+              at<float>(ws, L.dx));
   const int nt = (2 * S + 255) / 256;
-  hipLaunchKernelGGL(episode_prior_bwd_reduce_kernel, dim3(B + EP_H * nt + EP_H), dim3(256), 0, as_stream(stream), states, others,
-                     B, S, at<float>(ws, L.h1), at<float>(ws, L.h2), at<float>(ws, L.dz), at<float>(ws, L.dh1), at<float>(ws, L.dh2),
-                     at<float>(ws, L.dx), dstates, dw1, db1, dw2, db2, dw3, db3);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(episode_prior_bwd_reduce_kernel, dim3(B + EP_H * nt + EP_H), dim3(256), 0, as_stream(stream), states, others, B, S,
+              at<float>(ws, L.h1), at<float>(ws, L.h2), at<float>(ws, L.dz), at<float>(ws, L.dh1), at<float>(ws, L.dh2),
+              at<float>(ws, L.dx), dstates, dw1, db1, dw2, db2, dw3, db3);
   return 0;
 }

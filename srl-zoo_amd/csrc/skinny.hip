@@ -800,11 +800,8 @@ __global__ __launch_bounds__(256) void nchw_chan_sum_partial(const float* __rest
     s += (v[0] + v[1]) + (v[2] + v[3]);
   }
   for (int i = hw4 * 4 + threadIdx.x; i < HW; i += 256) s += plane[i];
-  double d = wave_sum_d((double)s);
-  __shared__ double sm[4];
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = d;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[(size_t)c * N + n] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+  const double d = block_sum_pairs_d((double)s);
+  if (threadIdx.x == 0) partial[(size_t)c * N + n] = d;
 }
 __global__ void nchw_chan_sum_final(const double* __restrict__ partial, int N, float* __restrict__ out) {
   const int c = blockIdx.x;
@@ -855,8 +852,8 @@ static int launch_conv(const PT* img, const float* w, float* feat, float* stats,
   do {                                                                                                                    \
     const size_t lds = conv_lds<K>(PIPED) + (sizeof(PT) == 1 ? 768 * 4 : 0);                                              \
     SRLZ_MAX_LDS((skinny_conv_kernel<K, PAD, BN, MU, PT>), lds);                                                          \
-    hipLaunchKernelGGL((skinny_conv_kernel<K, PAD, BN, MU, PT>), grid, block, lds, st, img, w, feat, stats, d->n, d->c,   \
-                       d->himg, d->wimg, d->hf, d->wf, ty, tx, y_raw, y_bnp, images_per_group(d), lut);                   \
+    SRLZ_LAUNCH((skinny_conv_kernel<K, PAD, BN, MU, PT>), grid, block, lds, st, img, w, feat, stats, d->n, d->c,          \
+                d->himg, d->wimg, d->hf, d->wf, ty, tx, y_raw, y_bnp, images_per_group(d), lut);                          \
   } while (0)
   bool launched = false;
   if constexpr (K == 4 && sizeof(PT) == 4) if (y_raw) {
@@ -867,7 +864,6 @@ static int launch_conv(const PT* img, const float* w, float* feat, float* stats,
     if (multi) SRLZ_CONV_LAUNCH(false, true, true); else SRLZ_CONV_LAUNCH(false, false, true);
   }
 #undef SRLZ_CONV_LAUNCH
-  SRLZ_LAUNCHED();
   return 0;
 }
 
@@ -894,18 +890,16 @@ static int launch_wgrad(const PT* img, const float* feat, float* dw, void* ws, s
   if (pfuse) pf = *pfuse;
   bool launched = false;
   if constexpr (K == 7) if (pf.y) {
-    hipLaunchKernelGGL((skinny_wgrad_kernel<K, PAD, true, PT>), dim3(g, d->c / 3), dim3(256), lds, st, img, feat, partial, d->n, d->c,
-                       d->himg, d->wimg, d->hf, d->wf, ty, tx, feat_bnp, pf, images_per_group(d), lut);
+    SRLZ_LAUNCH((skinny_wgrad_kernel<K, PAD, true, PT>), dim3(g, d->c / 3), dim3(256), lds, st, img, feat, partial, d->n, d->c, d->himg,
+                d->wimg, d->hf, d->wf, ty, tx, feat_bnp, pf, images_per_group(d), lut);
     launched = true;
   }
   if (!launched)
-    hipLaunchKernelGGL((skinny_wgrad_kernel<K, PAD, false, PT>), dim3(g, d->c / 3), dim3(256), lds, st, img, feat, partial, d->n, d->c,
-                       d->himg, d->wimg, d->hf, d->wf, ty, tx, feat_bnp, pf, images_per_group(d), lut);
-  SRLZ_LAUNCHED();
+    SRLZ_LAUNCH((skinny_wgrad_kernel<K, PAD, false, PT>), dim3(g, d->c / 3), dim3(256), lds, st, img, feat, partial, d->n, d->c, d->himg,
+                d->wimg, d->hf, d->wf, ty, tx, feat_bnp, pf, images_per_group(d), lut);
   const int total = (d->c / 3) * 64 * Geo<K>::KT;
-  hipLaunchKernelGGL(skinny_wgrad_reduce, dim3((total + WRED_OUTS - 1) / WRED_OUTS), dim3(1024), 0, st, partial, 2 * g, d->c, K * K, Geo<K>::KT,
-                     NT * 32, dw);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(skinny_wgrad_reduce, dim3((total + WRED_OUTS - 1) / WRED_OUTS), dim3(1024), 0, st, partial, 2 * g, d->c, K * K, Geo<K>::KT,
+              NT * 32, dw);
   return 0;
 }
 
@@ -946,9 +940,8 @@ extern "C" int srlz_conv1_bwd_data(const float* dy_nhwc, const float* w_ref, flo
   const int ntiles = d->n * ty * tx;
   const size_t lds = (size_t)128 * DG_TP * sizeof(float);
   SRLZ_MAX_LDS(conv1_dgrad_kernel, lds);
-  hipLaunchKernelGGL(conv1_dgrad_kernel, dim3(persistent_grid(ntiles), d->c / 3), dim3(256), lds, as_stream(stream), dy_nhwc,
-                     w_ref, dx_nchw, d->n, d->c, d->himg, d->wimg, d->hf, d->wf, ty, tx);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(conv1_dgrad_kernel, dim3(persistent_grid(ntiles), d->c / 3), dim3(256), lds, as_stream(stream), dy_nhwc, w_ref, dx_nchw, d->n,
+              d->c, d->himg, d->wimg, d->hf, d->wf, ty, tx);
   return 0;
 }
 
@@ -1020,11 +1013,8 @@ extern "C" int srlz_convT_out_bwd_weight(const float* x_nhwc, const float* dy_nc
     double* part = (double*)((char*)ws + wgrad_ws<4>(d) - (size_t)d->n * d->c * sizeof(double));
     SRLZ_REQUIRE((((uintptr_t)part) & 7) == 0 && ((d->himg * d->wimg) & 3) == 0, SRLZ_ERR_BAD_DESC,
                  "convT_out_bwd_weight: unaligned workspace / image plane");
-    hipLaunchKernelGGL(nchw_chan_sum_partial, dim3(d->n * d->c), dim3(256), 0, as_stream(stream), dy_nchw, d->c,
-                       d->himg * d->wimg, part, d->n);
-    SRLZ_LAUNCHED();
-    hipLaunchKernelGGL(nchw_chan_sum_final, dim3(d->c), dim3(64), 0, as_stream(stream), part, d->n, dbias);
-    SRLZ_LAUNCHED();
+    SRLZ_LAUNCH(nchw_chan_sum_partial, dim3(d->n * d->c), dim3(256), 0, as_stream(stream), dy_nchw, d->c, d->himg * d->wimg, part, d->n);
+    SRLZ_LAUNCH(nchw_chan_sum_final, dim3(d->c), dim3(64), 0, as_stream(stream), part, d->n, dbias);
   }
   return 0;
 }

@@ -32,16 +32,8 @@ __global__ __launch_bounds__(MSE_THREADS) void mse_target_kernel(const float* __
     acc += (double)d * (double)d;
     dpred_unit[i] = d * two_over_n;
   }
-  acc = wave_sum_d(acc);
-  __shared__ double sm[MSE_THREADS / 64];
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < MSE_THREADS / 64; ++w) s += sm[w];
-    loss[0] = (float)(s / (double)n);
-  }
+  const double s = block_sum_d<MSE_THREADS / 64>(acc);
+  if (threadIdx.x == 0) loss[0] = (float)(s / (double)n);
 }
 
 // y = (x * mask) / keep, the fp32 operations of `x * mask / (1 - p)` in that order (mask: 0 or 1 per element)
@@ -73,8 +65,7 @@ static int dropout_launch(const char* what, const float* x, const unsigned char*
   const long long n = (long long)rows * cols;
   long long blocks = ((n + 3) / 4 + 255) / 256;
   if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(dropout_kernel, dim3((int)blocks), dim3(256), 0, st, x, mask, keep, y, n);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(dropout_kernel, dim3((int)blocks), dim3(256), 0, st, x, mask, keep, y, n);
   return 0;
 }
 
@@ -88,9 +79,7 @@ extern "C" int srlz_mse_target_fwd(const float* pred, const float* target, int B
   SRLZ_REQUIRE(n <= MSE_MAX, SRLZ_ERR_BAD_DESC, "mse_target_fwd: B * S = %lld exceeds the %lld elements one launch takes", n, MSE_MAX);
   SRLZ_REQUIRE((((uintptr_t)pred | (uintptr_t)target | (uintptr_t)dpred_unit) & 15) == 0, SRLZ_ERR_BAD_DESC,
                "mse_target_fwd: pred / target / dpred_unit must be 16-byte aligned");
-  hipLaunchKernelGGL(mse_target_kernel, dim3(1), dim3(MSE_THREADS), 0, as_stream(stream), pred, target, n, 2.0f / (float)n, loss,
-                     dpred_unit);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(mse_target_kernel, dim3(1), dim3(MSE_THREADS), 0, as_stream(stream), pred, target, n, 2.0f / (float)n, loss, dpred_unit);
   return 0;
 }
 

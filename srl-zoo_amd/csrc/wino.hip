@@ -284,8 +284,7 @@ __global__ __launch_bounds__(256) void conv64_wino_poolsum_zero_scale_kernel(con
   const int g = blockIdx.y;
   const float* __restrict__ rec = ps.bnp + g * 256;
   const int c4 = threadIdx.x & 15;
-  const f32x4 mean = *(const f32x4*)(rec + c4 * 4), pinv = *(const f32x4*)(rec + 64 + c4 * 4);
-  const f32x4 psc = *(const f32x4*)(rec + 128 + c4 * 4), psh = *(const f32x4*)(rec + 192 + c4 * 4);
+  const auto [mean, pinv, psc, psh] = load_bn_quads(rec, c4);
   unsigned zmask = 0;
 #pragma unroll
   for (int j = 0; j < 4; ++j) zmask |= ((fabsf(psc[j]) <= 1e-3f * fabsf(psh[j]) || psc[j] == 0.f) ? 1u : 0u) << j;
@@ -311,17 +310,7 @@ __global__ __launch_bounds__(256) void conv64_wino_poolsum_zero_scale_kernel(con
         }
     }
   }
-  __shared__ double sm[16][128];
-  const int prow = threadIdx.x >> 4;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { sm[prow][c4 * 4 + j] = s1[j]; sm[prow][64 + c4 * 4 + j] = s2[j]; }
-  __syncthreads();
-  if (threadIdx.x < 128) {
-    double t = 0.0;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) t += sm[r][threadIdx.x];
-    partial[((size_t)g * rows + first_row + blockIdx.x) * 128 + threadIdx.x] = (float)t;
-  }
+  bn_bwd_combine_store(s1, s2, partial + ((size_t)g * rows + first_row + blockIdx.x) * 128);
 }
 
 template <bool PSUM, bool FUSE>
@@ -801,8 +790,7 @@ extern "C" size_t srlz_conv64_wino_packed_floats(void) { return (size_t)4 * WN_C
 
 extern "C" int srlz_conv64_wino_pack_weights(const float* w_ref, float* upack_fwd, float* upack_bwd, srlz_stream_t stream) {
   SRLZ_REQUIRE(w_ref && (upack_fwd || upack_bwd), SRLZ_ERR_NULL, "conv64_wino_pack_weights: null pointer");
-  hipLaunchKernelGGL(conv64_wino_pack_kernel, dim3(16), dim3(256), 0, as_stream(stream), w_ref, upack_fwd, upack_bwd);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(conv64_wino_pack_kernel, dim3(16), dim3(256), 0, as_stream(stream), w_ref, upack_fwd, upack_bwd);
   return 0;
 }
 
@@ -823,19 +811,17 @@ static int wino_launch(const float* x, const float* upack, const float* bias, fl
   hipStream_t st = as_stream(stream);
   if (ps) {
     SRLZ_MAX_LDS((conv64_wino_kernel<true, false>), lds);
-    hipLaunchKernelGGL((conv64_wino_kernel<true, false>), dim3(grid), dim3(WN_THREADS), lds, st, x, upack, bias, y, partial, P, ntiles, *ps, x_bnp);
+    SRLZ_LAUNCH((conv64_wino_kernel<true, false>), dim3(grid), dim3(WN_THREADS), lds, st, x, upack, bias, y, partial, P, ntiles, *ps, x_bnp);
   } else if (x_bnp) {
     SRLZ_MAX_LDS((conv64_wino_kernel<false, true>), lds);
-    hipLaunchKernelGGL((conv64_wino_kernel<false, true>), dim3(grid), dim3(WN_THREADS), lds, st, x, upack, bias, y, partial, P, ntiles, none, x_bnp);
+    SRLZ_LAUNCH((conv64_wino_kernel<false, true>), dim3(grid), dim3(WN_THREADS), lds, st, x, upack, bias, y, partial, P, ntiles, none, x_bnp);
   } else {
     SRLZ_MAX_LDS((conv64_wino_kernel<false, false>), lds);
-    hipLaunchKernelGGL((conv64_wino_kernel<false, false>), dim3(grid), dim3(WN_THREADS), lds, st, x, upack, bias, y, partial, P, ntiles, none, x_bnp);
+    SRLZ_LAUNCH((conv64_wino_kernel<false, false>), dim3(grid), dim3(WN_THREADS), lds, st, x, upack, bias, y, partial, P, ntiles, none, x_bnp);
   }
-  SRLZ_LAUNCHED();
   if (ps) {  // the records of the channels the main kernel cannot sum from the pooled value (normally: zeros)
-    hipLaunchKernelGGL(conv64_wino_poolsum_zero_scale_kernel, dim3(WN_ZBLOCKS, P.G), dim3(256), 0, st, (const float*)y, *ps, partial,
-                       P.N, P.H, P.W, P.gstride, P.tpg + WN_ZBLOCKS, P.tpg);
-    SRLZ_LAUNCHED();
+    SRLZ_LAUNCH(conv64_wino_poolsum_zero_scale_kernel, dim3(WN_ZBLOCKS, P.G), dim3(256), 0, st, (const float*)y, *ps, partial, P.N, P.H,
+                P.W, P.gstride, P.tpg + WN_ZBLOCKS, P.tpg);
   }
   return 0;
 }
@@ -900,13 +886,10 @@ extern "C" int srlz_conv64_wino_bwd_weight(const float* x, const float* dy, floa
   hipStream_t st = as_stream(stream);
   const size_t lds = (size_t)4 * WG_OP * 4;
   SRLZ_MAX_LDS(conv64_wino_wgrad_kernel, lds);
-  hipLaunchKernelGGL(conv64_wino_wgrad_kernel, dim3(grid), dim3(256), lds, st, x, dy, (float*)ws, P);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(conv64_wino_wgrad_kernel, dim3(grid), dim3(256), lds, st, x, dy, (float*)ws, P);
   double* mid = (double*)((char*)ws + part_bytes);
   const int npair = grid >> 1, per = (npair + WG_CHUNKS - 1) / WG_CHUNKS;
-  hipLaunchKernelGGL(conv64_wino_wgrad_reduce_a, dim3(65536 / 256, WG_CHUNKS), dim3(256), 0, st, (const float*)ws, mid, grid, per);
-  SRLZ_LAUNCHED();
-  hipLaunchKernelGGL(conv64_wino_wgrad_reduce_b, dim3(256), dim3(256), 0, st, (const double*)mid, WG_CHUNKS, dw_ref);
-  SRLZ_LAUNCHED();
+  SRLZ_LAUNCH(conv64_wino_wgrad_reduce_a, dim3(65536 / 256, WG_CHUNKS), dim3(256), 0, st, (const float*)ws, mid, grid, per);
+  SRLZ_LAUNCH(conv64_wino_wgrad_reduce_b, dim3(256), dim3(256), 0, st, (const double*)mid, WG_CHUNKS, dw_ref);
   return 0;
 }
