@@ -9,7 +9,7 @@
  *
  * Conventions
  *   - plain C types only; every pointer is a DEVICE pointer unless the name ends in _host.
- *   - all floating point data is fp32; activations are NHWC ([N][H][W][C], C fastest) unless stated NCHW.
+ *   - all floating point data is fp32 (srlz_knn_f64, the evaluation search, alone takes fp64); activations are NHWC ([N][H][W][C], C fastest) unless stated NCHW.
  *     The reference's tensors are NCHW ([B,C,D1,D2]; D1/D2 are the image's W/H because the loader transposes,
  *     preprocessing/data_loader.py:255); the NCHW<->NHWC change happens INSIDE conv1 (reads NCHW) and the last
  *     ConvTranspose (writes NCHW), so callers only ever hand over / receive reference-layout images.
@@ -675,6 +675,26 @@ int srlz_mse_target_fwd(const float* pred, const float* target, int B, int S, fl
  * bwd: dx = dy * mask / keep.  Any rows >= 1, cols >= 1; in place allowed.  Eval mode calls neither. */
 int srlz_dropout_fwd(const float* x, const unsigned char* mask, float keep, float* y, int rows, int cols, srlz_stream_t stream);
 int srlz_dropout_bwd(const float* dy, const unsigned char* mask, float keep, float* dx, int rows, int cols, srlz_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Evaluation: exact k nearest neighbours in fp64 (csrc/knn.hip).  Replaces
+ *   NearestNeighbors(n_neighbors=k + 1, algorithm='ball_tree').fit(states).kneighbors(states)      evaluation/knn_images.py:83-84
+ * The only fp64 tensors of this ABI: the states of states_rewards.npz are float32 and convert exactly, --ground-truth searches the
+ * dataset's float64 states unrounded.
+ *   dist2(q, x) = sum_d (q_d - x_d)^2 in fp64, ONE chain acc = fma(q_d - x_d, q_d - x_d, acc) over d = 0 .. D-1 (the differences
+ *   form, never |q|^2 + |x|^2 - 2 q.x); the chain of a pair is the same whatever the tiling, so neither the value nor the order
+ *   depends on launch geometry, on Q or on how the database is split.
+ *   Row r of idx / dist2 [Q, K]: the K rows of db [N, D] with the smallest key (dist2, index) for queries[r], compared
+ *   lexicographically, ascending — equal distances go to the lower index.  queries [Q, D] may alias db; nothing is special-cased (a
+ *   query that is a database row finds itself at distance 0).  No float atomics, every merge has one order: repeated calls are
+ *   bit-identical.  Inputs must be finite (a NaN distance never enters a list).
+ * 1 <= K <= 32, K <= N, D >= 1 (no upper limit on D: the dimensions pass through the chip 64 at a time), Q >= 1, N * D and Q * K
+ * below 2^31; anything else is SRLZ_ERR_BAD_DESC, a null pointer SRLZ_ERR_NULL, ws_bytes < srlz_knn_workspace(N, Q, D, K)
+ * SRLZ_ERR_WORKSPACE — all before any launch.  srlz_knn_workspace returns 0 for a shape the launcher rejects.
+ * ------------------------------------------------------------------------------------------------------------ */
+size_t srlz_knn_workspace(int N, int Q, int D, int K);
+int srlz_knn_f64(const double* db /*[N,D]*/, int N, const double* queries /*[Q,D]*/, int Q, int D, int K, int* idx /*[Q,K]*/,
+                 double* dist2 /*[Q,K]*/, void* ws, size_t ws_bytes, srlz_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Debug / calibration hooks (not on the product path).

@@ -79,6 +79,22 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
+// (d, i) before (e, j) in the order of the key (value, index): smaller value first, equal values by the lower index
+__device__ __forceinline__ bool key_less_d(double d, int i, double e, int j) { return d < e || (d == e && i < j); }
+
+// Minimum of (d, i) by that key over the wave, left in every lane.  A comparison, not a sum: the result is the same in any order.
+__device__ __forceinline__ void wave_min_key_d(double& d, int& i) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double e = __shfl_xor(d, o, 64);
+    const int j = __shfl_xor(i, o, 64);
+    if (key_less_d(e, j, d, i)) {
+      d = e;
+      i = j;
+    }
+  }
+}
+
 // Sum of v over a block of NWAVES waves in a fixed order (deterministic): fp64 wave sums, one LDS slot per wave, one barrier.
 // Contract: blockDim.x == 64 * NWAVES, EVERY thread of the block calls it, at most once per kernel (the slots are not
 // re-armed); the sums are meant for thread 0.  block_wave_sums_d returns the slots, block_sum_d adds them left to right,

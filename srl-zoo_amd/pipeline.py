@@ -1,13 +1,17 @@
 """The three helpers train.py imports from the reference's pipeline.py (getLogFolderName :28-51, saveConfig :223-236,
-correlationCall) plus the exit-code constants (:23-25).  The grid-search driver itself is out of scope."""
+correlationCall) plus the exit-code constants (:23-25), and the KNN-MSE evaluation call with its two helpers (knnCall :194-220,
+createGroundTruthFolder :166-177, useRelativePosition :239-246).  The grid-search driver itself is out of scope."""
 from __future__ import print_function, division
 
 import datetime
 import json
+import os
+import subprocess
+import sys
 from collections import OrderedDict
 from pprint import pprint
 
-from utils import printBlue, printYellow, createFolder
+from utils import printBlue, printGreen, printRed, printYellow, createFolder
 
 MATPLOTLIB_WARNING_CODE = -11
 NO_PAIRS_ERROR = 10  # no dissimilar/reference pairs found (robotic priors)
@@ -42,3 +46,60 @@ def correlationCall(exp_config, plot=False):
     """The reference shells out to plotting.representation_plot for the ground-truth correlation; plotting and
     evaluation are outside this build's scope, so this only says so."""
     printYellow("correlationCall: ground-truth correlation (plotting/) is out of scope of the MI355X hot-path build")
+
+
+def printConfigOnError(return_code, exp_config, step_name):
+    """Reference pipeline.py:54-64."""
+    if return_code != 0:
+        printRed("An error occured, error code: {}".format(return_code))
+        pprint(exp_config)
+        raise RuntimeError("Error during {} (config file above)".format(step_name))
+    print("End of " + step_name)
+
+
+def createGroundTruthFolder(exp_config):
+    """logs/<dataset>/baselines/ground_truth/ with its exp_config.json, so that KNN-MSE can be computed for the ground truth.
+    :return: (dict) exp_config with 'log-folder' and 'ground-truth' set"""
+    log_folder = "logs/{}/baselines/ground_truth/".format(exp_config['data-folder'])
+    createFolder(log_folder, "")
+    exp_config['log-folder'] = log_folder
+    exp_config['ground-truth'] = True
+    saveConfig(exp_config)
+    return exp_config
+
+
+def useRelativePosition(data_folder):
+    """The dataset's 'relative_pos' setting (data/<folder>/dataset_config.json)."""
+    with open('data/{}/dataset_config.json'.format(data_folder), 'r') as f:
+        relative_pos = json.load(f).get('relative_pos', False)
+    return relative_pos
+
+
+def knnCall(exp_config):
+    """KNN-MSE of the representation in exp_config['log-folder'] (writes knn_mse.json there): evaluation.knn_images in a fresh child
+    process with the reference's argument list.  The child is this interpreter and finds the package whatever the working
+    directory (the dataset is looked up under ./data, as everywhere)."""
+    folder_path = '{}/NearestNeighbors/'.format(exp_config['log-folder'])
+    createFolder(folder_path, "NearestNeighbors folder already exist")
+
+    printGreen("\nEvaluating the state representation with KNN")
+
+    args = ['--seed', str(exp_config['knn-seed']), '--n-samples', str(exp_config['knn-samples'])]
+
+    if exp_config.get('ground-truth', False):
+        args.extend(['--ground-truth'])
+
+    if exp_config.get('multi-view', False):
+        args.extend(['--multi-view'])
+
+    if exp_config.get('relative-pos', False):
+        args.extend(['--relative-pos'])
+
+    for arg in ['log-folder', 'n-neighbors', 'n-to-plot']:
+        args.extend(['--{}'.format(arg), str(exp_config[arg])])
+
+    env = dict(os.environ)
+    package = os.path.dirname(os.path.abspath(__file__))
+    env["PYTHONPATH"] = package + (os.pathsep + env["PYTHONPATH"] if env.get("PYTHONPATH") else "")
+    ok = subprocess.call([sys.executable, '-m', 'evaluation.knn_images'] + args, env=env)
+    printConfigOnError(ok, exp_config, "knnCall")

@@ -1787,6 +1787,55 @@ class ConcatOneHotFn(Function):
         return dcat[:, :ctx.sdim].contiguous(), None, None
 
 
+def _knn_host_array(a, name):
+    """numpy / torch, float32 / float64, 2-D, finite -> C-contiguous float64 numpy (an exact conversion)."""
+    import numpy as np
+    if torch.is_tensor(a):
+        a = a.detach().cpu().numpy()
+    a = np.asarray(a)
+    if a.dtype not in (np.float32, np.float64):
+        raise ValueError("knn: %s must be float32 or float64 (got %s)" % (name, a.dtype))
+    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("knn: %s must be a non-empty [rows, D] array (got shape %s)" % (name, a.shape))
+    if not np.isfinite(a).all():
+        raise ValueError("knn: %s holds NaN or infinite values" % name)
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+KNN_MAX_K = 32  # include/srlz.h, srlz_knn_f64
+
+
+def knn(db, k, queries=None):
+    """The k nearest rows of `db` [N, D] for every row of `queries` [Q, D] (None: the database itself, so every row finds itself
+    first) — the exact fp64 search of csrc/knn.hip in place of the reference's ball tree (evaluation/knn_images.py:83-84).
+    numpy or torch, float32 or float64; uploaded as fp64.  Order: (dist2, index) ascending, equal distances to the lower index.
+    :return: (idx int64 [Q, k], dist2 float64 [Q, k]) as CPU numpy — SQUARED distances.
+    ValueError: non-finite input, mismatched D, k outside [1, min(32, N)].  RuntimeError without a GPU: there is no CPU fallback."""
+    import numpy as np
+    dbh = _knn_host_array(db, "db")
+    qh = dbh if queries is None else _knn_host_array(queries, "queries")
+    if qh.shape[1] != dbh.shape[1]:
+        raise ValueError("knn: queries have D = %d, the database D = %d" % (qh.shape[1], dbh.shape[1]))
+    k = int(k)
+    n, d = dbh.shape
+    nq = qh.shape[0]
+    if k < 1 or k > n or k > KNN_MAX_K:
+        raise ValueError("knn: k must lie in [1, min(%d, N)] (k = %d, N = %d)" % (KNN_MAX_K, k, n))
+    if n * d >= 2 ** 31 or nq * k >= 2 ** 31:
+        raise ValueError("knn: N * D and Q * k must stay below 2^31 (N = %d, D = %d, Q = %d, k = %d)" % (n, d, nq, k))
+    if not torch.cuda.is_available():
+        raise C.SrlzError("knn runs on the GPU only (torch.cuda.is_available() is False): the srl-zoo_amd build has no CPU fallback")
+    device = torch.device("cuda", torch.cuda.current_device())
+    db_d = torch.from_numpy(dbh).to(device)
+    q_d = db_d if queries is None else torch.from_numpy(qh).to(device)
+    idx = torch.empty((nq, k), dtype=torch.int32, device=device)
+    dist2 = torch.empty((nq, k), dtype=torch.float64, device=device)
+    nbytes = C.knn_workspace(n, nq, d, k)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+    C.knn_f64(ptr(db_d), n, ptr(q_d), nq, d, k, ptr(idx), ptr(dist2), ptr(ws), nbytes, stream())
+    return idx.cpu().numpy().astype(np.int64), dist2.cpu().numpy()
+
+
 def normalize_u8(frames, out=None):
     """uint8 [N,H,W,C] device tensor -> normalised fp32 [N,C,W,H] (the reference's observation tensor); `out`: where to
     write it (a contiguous [N,C,W,H] fp32 tensor, e.g. one half of a pair buffer)."""
