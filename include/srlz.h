@@ -9,7 +9,7 @@
  *
  * Conventions
  *   - plain C types only; every pointer is a DEVICE pointer unless the name ends in _host.
- *   - all floating point data is fp32 (srlz_knn_f64, the evaluation search, alone takes fp64); activations are NHWC ([N][H][W][C], C fastest) unless stated NCHW.
+ *   - all floating point data is fp32 (only srlz_knn_f64, the evaluation search, and srlz_pca_*, the PCA baseline, take fp64); activations are NHWC ([N][H][W][C], C fastest) unless stated NCHW.
  *     The reference's tensors are NCHW ([B,C,D1,D2]; D1/D2 are the image's W/H because the loader transposes,
  *     preprocessing/data_loader.py:255); the NCHW<->NHWC change happens INSIDE conv1 (reads NCHW) and the last
  *     ConvTranspose (writes NCHW), so callers only ever hand over / receive reference-layout images.
@@ -679,7 +679,7 @@ int srlz_dropout_bwd(const float* dy, const unsigned char* mask, float keep, flo
 /* ------------------------------------------------------------------------------------------------------------
  * Evaluation: exact k nearest neighbours in fp64 (csrc/knn.hip).  Replaces
  *   NearestNeighbors(n_neighbors=k + 1, algorithm='ball_tree').fit(states).kneighbors(states)      evaluation/knn_images.py:83-84
- * The only fp64 tensors of this ABI: the states of states_rewards.npz are float32 and convert exactly, --ground-truth searches the
+ * fp64 tensors (with srlz_pca_* the only ones of this ABI): the states of states_rewards.npz are float32 and convert exactly, --ground-truth searches the
  * dataset's float64 states unrounded.
  *   dist2(q, x) = sum_d (q_d - x_d)^2 in fp64, ONE chain acc = fma(q_d - x_d, q_d - x_d, acc) over d = 0 .. D-1 (the differences
  *   form, never |q|^2 + |x|^2 - 2 q.x); the chain of a pair is the same whatever the tiling, so neither the value nor the order
@@ -695,6 +695,44 @@ int srlz_dropout_bwd(const float* dy, const unsigned char* mask, float keep, flo
 size_t srlz_knn_workspace(int N, int Q, int D, int K);
 int srlz_knn_f64(const double* db /*[N,D]*/, int N, const double* queries /*[Q,D]*/, int Q, int D, int K, int* idx /*[Q,K]*/,
                  double* dist2 /*[Q,K]*/, void* ws, size_t ws_bytes, srlz_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * PCA baseline: sklearn's IncrementalPCA in fp64 through a Gram matrix (csrc/pca.hip).  Replaces, per minibatch,
+ *   ipca.partial_fit(toNumpyMatrix(obs_var))      srl_baselines/pca.py:107-108   (one LAPACK SVD of a (k + bs + 1) x D matrix)
+ *   ipca.transform(toNumpyMatrix(obs_var))        srl_baselines/pca.py:117-118
+ * State, all fp64 on the device: running mean [D] and var [D], basis [k, D] = singular_values_[:, None] * components_.
+ * Frames come in one of two forms, EXACTLY ONE of x_u8 / x_f32 non-null: x_u8 = the loader's planar bytes [m, C, plane] with
+ * norm_lut = the srlz_normalize_lut table (channel c reads row c % 3; C = D / plane in {3, 6, 9}), or x_f32 [m, D].
+ * The matrix A sklearn decomposes (sklearn 1.7 decomposition/_incremental_pca.py:343-360, partial_fit: "Whitening" ... np.vstack) is never
+ * written: first minibatch (first != 0) A = X - bmean, m rows; later A = [ basis ; X - bmean ; corr ], r = k + m + 1 rows.
+ * Every sum has one order and there are no float atomics: repeated calls are bit-identical.
+ * Rejected before any launch (SRLZ_ERR_BAD_DESC, text in srlz_last_error): m < 1, k < 1, k > D, k > m on the first minibatch, more
+ * than 65535 output tiles of 16 x 16; a missing pointer is SRLZ_ERR_NULL, a short workspace SRLZ_ERR_WORKSPACE.
+ * ------------------------------------------------------------------------------------------------------------ */
+/* Bytes of partials for the Gram matrix of a `rows`-row A (srlz_pca_gram) / for srlz_pca_transform; 0 for a rejected shape. */
+size_t srlz_pca_workspace(int rows, int D);
+size_t srlz_pca_transform_workspace(int M, int k, int D);
+/* sklearn.utils.extmath._incremental_mean_and_var (utils/extmath.py:1064-1187, called at _incremental_pca.py:335) per column, and what partial_fit derives from it:
+ * mean / var [D] are updated in place from n_seen samples to n_seen + m (n_seen == 0: their contents are not read);
+ * bmean [D] = the batch mean (np.mean(X, axis=0)); corr [D] = sqrt(n_seen / (n_seen + m) * m) * (mean_old - bmean), the
+ * mean_correction row (zeros on the first minibatch). */
+int srlz_pca_stats(const uint8_t* x_u8, const float* x_f32, const float* norm_lut, int plane, int m, int D, long long n_seen,
+                   double* mean, double* var, double* bmean, double* corr, srlz_stream_t stream);
+/* G [r, r] = A Aᵀ, exactly symmetric — what replaces linalg.svd(X, full_matrices=False) of partial_fit (_incremental_pca.py:362): the eigenpairs (w, u) of G
+ * give S = sqrt(w) and S_i V_i = u_iᵀ A.  v_mfma_f64_16x16x4_f64 over the lower triangle of 16 x 16 tiles, D split over
+ * workgroups, partials in ws summed in chunk order.  ws_bytes >= srlz_pca_workspace(r, D). */
+int srlz_pca_gram(const double* basis /*[k,D]*/, int k, int first, const uint8_t* x_u8, const float* x_f32, const float* norm_lut,
+                  int plane, int m, const double* bmean /*[D]*/, const double* corr /*[D]*/, int D, double* G /*[r,r]*/, void* ws,
+                  size_t ws_bytes, srlz_stream_t stream);
+/* out [k, D] = W [k, r] A (W = the k leading eigenvectors as rows): the new basis S·V.  out must not be the basis being read. */
+int srlz_pca_project(const double* W /*[k,r]*/, const double* basis /*[k,D]*/, int k, int first, const uint8_t* x_u8,
+                     const float* x_f32, const float* norm_lut, int plane, int m, const double* bmean, const double* corr, int D,
+                     double* out /*[k,D]*/, srlz_stream_t stream);
+/* IncrementalPCA.transform (sklearn decomposition/_base.py:116-145: (X - mean_) @ components_.T): states [M, k] fp32 =
+ * (X - mean) (basis / S)ᵀ accumulated in fp64; a component with S_i <= 0 gives zeros.  ws_bytes >= srlz_pca_transform_workspace. */
+int srlz_pca_transform(const uint8_t* x_u8, const float* x_f32, const float* norm_lut, int plane, int M, const double* mean /*[D]*/,
+                       const double* basis /*[k,D]*/, const double* S /*[k]*/, int k, int D, float* states /*[M,k]*/, void* ws,
+                       size_t ws_bytes, srlz_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Debug / calibration hooks (not on the product path).

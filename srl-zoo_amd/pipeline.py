@@ -1,6 +1,7 @@
 """The three helpers train.py imports from the reference's pipeline.py (getLogFolderName :28-51, saveConfig :223-236,
-correlationCall) plus the exit-code constants (:23-25), and the KNN-MSE evaluation call with its two helpers (knnCall :194-220,
-createGroundTruthFolder :166-177, useRelativePosition :239-246).  The grid-search driver itself is out of scope."""
+correlationCall) plus the exit-code constants (:23-25), the KNN-MSE evaluation call with its two helpers (knnCall :194-220,
+createGroundTruthFolder :166-177, useRelativePosition :239-246) and the PCA baseline call (pcaCall :150-163).  The grid-search driver
+itself is out of scope."""
 from __future__ import print_function, division
 
 import datetime
@@ -75,6 +76,33 @@ def useRelativePosition(data_folder):
     return relative_pos
 
 
+def _childEnv():
+    """The environment of a child interpreter that finds the package whatever the working directory."""
+    env = dict(os.environ)
+    package = os.path.dirname(os.path.abspath(__file__))
+    env["PYTHONPATH"] = package + (os.pathsep + env["PYTHONPATH"] if env.get("PYTHONPATH") else "")
+    return env
+
+
+def pcaArguments(exp_config):
+    """The reference's argument list for srl_baselines.pca (pipeline.py:156-160)."""
+    args = ['--no-display-plots']
+    config_args = ['data-folder', 'training-set-size', 'state-dim']
+
+    for arg in config_args:
+        args.extend(['--{}'.format(arg), str(exp_config[arg])])
+    return args
+
+
+def pcaCall(exp_config):
+    """The PCA baseline on exp_config's dataset (reference pipeline.py:150-163): srl_baselines.pca in a fresh child process — this
+    interpreter, as knnCall starts its child.
+    :param exp_config: (dict)"""
+    printGreen("\n Baseline PCA...")
+    ok = subprocess.call([sys.executable, '-m', 'srl_baselines.pca'] + pcaArguments(exp_config), env=_childEnv())
+    printConfigOnError(ok, exp_config, "pcaCall")
+
+
 def knnCall(exp_config):
     """KNN-MSE of the representation in exp_config['log-folder'] (writes knn_mse.json there): evaluation.knn_images in a fresh child
     process with the reference's argument list.  The child is this interpreter and finds the package whatever the working
@@ -98,8 +126,5 @@ def knnCall(exp_config):
     for arg in ['log-folder', 'n-neighbors', 'n-to-plot']:
         args.extend(['--{}'.format(arg), str(exp_config[arg])])
 
-    env = dict(os.environ)
-    package = os.path.dirname(os.path.abspath(__file__))
-    env["PYTHONPATH"] = package + (os.pathsep + env["PYTHONPATH"] if env.get("PYTHONPATH") else "")
-    ok = subprocess.call([sys.executable, '-m', 'evaluation.knn_images'] + args, env=env)
+    ok = subprocess.call([sys.executable, '-m', 'evaluation.knn_images'] + args, env=_childEnv())
     printConfigOnError(ok, exp_config, "knnCall")

@@ -193,6 +193,12 @@ _PROTOS = {
     "srlz_episode_prior_bwd": (c_int, [P, P, P, P, c_int, c_int, P, P, P, P, c_size_t, P, P, P, P, P, P, P, P]),
     "srlz_knn_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
     "srlz_knn_f64": (c_int, [P, c_int, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
+    "srlz_pca_workspace": (c_size_t, [c_int, c_int]),
+    "srlz_pca_transform_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "srlz_pca_stats": (c_int, [P, P, P, c_int, c_int, c_int, c_longlong, P, P, P, P, P]),
+    "srlz_pca_gram": (c_int, [P, c_int, c_int, P, P, P, c_int, c_int, P, P, c_int, P, P, c_size_t, P]),
+    "srlz_pca_project": (c_int, [P, P, c_int, c_int, P, P, P, c_int, c_int, P, P, c_int, P, P]),
+    "srlz_pca_transform": (c_int, [P, P, P, c_int, c_int, P, P, P, c_int, c_int, P, P, c_size_t, P]),
     "srlz_mse_target_fwd": (c_int, [P, P, c_int, c_int, P, P, P]),
     "srlz_dropout_fwd": (c_int, [P, P, c_float, P, c_int, c_int, P]),
     "srlz_dropout_bwd": (c_int, [P, P, c_float, P, c_int, c_int, P]),
