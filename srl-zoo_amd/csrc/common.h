@@ -67,6 +67,43 @@ __device__ __forceinline__ unsigned mad_u24(unsigned a, int b_uniform, unsigned 
   return r;
 }
 
+// Granlund-Montgomery division by an invariant for 31-bit dividends: l = ceil(log2 d), m = floor(2^(31+l) / d) + 1 (< 2^32),
+// q / d == umulhi(q, m) >> (l - 1) for every 0 <= q < 2^31 (d >= 2).  A run-time integer division is ~20 VALU instructions.
+static inline void fastdiv_init(unsigned d, unsigned* m, int* sh) {
+  int l = 0;
+  while ((1u << l) < d) ++l;
+  if (l == 0) l = 1;  // d == 1: m = 2^32 does not fit; callers have d >= 2
+  *m = (unsigned)((((unsigned long long)1 << (31 + l)) / d) + 1);
+  *sh = l - 1;
+}
+__device__ __forceinline__ int fastdiv(int q, unsigned m, int sh) { return (int)(__umulhi((unsigned)q, m) >> sh); }
+
+// A buffer resource over `bytes` bytes at `p` (raw, unstrided): a buffer access whose offset lies outside is DROPPED by the hardware
+// (a load returns 0), which makes a conditional access branch-free — the lane that must not write passes its file's *_DROP offset.
+// That matters beyond the branch itself: vmcnt counts stores too and is in-order, and behind a store inside a branch hipcc can only
+// wait for everything, so every later wait for a prefetch would also wait for these stores' HBM round trip.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t raw_buffer(const void* p, unsigned bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
+}
+
+// Epilogue option of the conv2 / conv3 data-gradient launches, whose output is the gradient of a POOLED map (conv64_dgrad_poolsum_kernel,
+// conv64_wino_kernel<.., true>): instead of BatchNorm-forward statistics the tile's partial record receives the two BatchNorm-BACKWARD
+// sums of the block that produced the pooled map,  sum dz  and  sum dz*xhat  with dz = d pooled where pooled > 0 (the gradient lives at
+// the window's argmax, and the pooled value IS relu(bn(y)) there: xhat follows from it) — what bn_relu_pool_bwd_reduce computes in a
+// pass of its own over (d pooled, pooled, argmax).  y / argmax are only touched for channels whose BatchNorm scale is (almost) 0 (xhat
+// cannot be recovered from the pooled value there).
+namespace {
+struct PoolSum {
+  const float* pooled;    // [N,Hd,Wd,64] like the launch's dst; NULL = off
+  const float* bnp;       // records of the pooled block's BatchNorm (256 floats per group)
+  const float* y;         // raw convolution output under the pooling [N,H,W,64]
+  const uint8_t* argmax;  // [N,Hd,Wd,64]
+  long long y_gstride;    // floats between two groups' images in y
+  int H, W, pad;
+};
+}  // namespace
+#define SRLZ_NO_POOLSUM PoolSum{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

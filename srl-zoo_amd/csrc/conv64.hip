@@ -38,6 +38,7 @@ namespace {
 constexpr int TM = 128;       // grid positions per forward tile
 constexpr int BATCH_FWD = SRLZ_BATCH_FWD;  // rows (of 16 lanes) a thread requests per round trip of a plain / forward-fused staging
 constexpr int NTAPS = 9;
+constexpr int WGRAD_PARTIAL_FLOATS = NTAPS * 4096 + 64;  // one workgroup's weight-gradient partial: nine 64 x 64 tap blocks, 64 bias sums
 
 struct ConvProg {
   int N, PH, PW, PHW, total_q;  // N / total_q: images / grid positions of ONE BatchNorm group
@@ -53,21 +54,6 @@ struct ConvProg {
   int dbg;         // ablation switches for tools/kbench.py (env SRLZ_ABLATE): 1 skip A staging, 2 skip epilogue
   unsigned mPHW, mPW;  // q / PHW and r / PW for 0 <= q, r < 2^31 as (__umulhi(q, m) >> sh): a run-time integer division is ~20
   int sPHW, sPW;       // VALU instructions and a reciprocal the compiler keeps in a register for the whole kernel (fastdiv)
-};
-
-// Granlund-Montgomery division by an invariant for 31-bit dividends: l = ceil(log2 d), m = floor(2^(31+l) / d) + 1 (< 2^32),
-// q / d == umulhi(q, m) >> (l - 1) for every 0 <= q < 2^31 (d >= 2).
-static void fastdiv_init(unsigned d, unsigned* m, int* sh) {
-  int l = 0;
-  while ((1u << l) < d) ++l;
-  if (l == 0) l = 1;  // d == 1: m = 2^32 does not fit; callers have d >= 2 (checked in build_program)
-  *m = (unsigned)((((unsigned long long)1 << (31 + l)) / d) + 1);
-  *sh = l - 1;
-}
-__device__ __forceinline__ int fastdiv(int q, unsigned m, int sh) { return (int)(__umulhi((unsigned)q, m) >> sh); }
-
-struct Axis {
-  int cls[3], d[3];  // per kernel index ky: class (parity) and grid offset
 };
 
 // GATHER: out[o] = sum_k in[o*s - p + k];  SCATTER: out[o] = sum_{k: (o+p-k)%s==0} in[(o+p-k)/s]
@@ -197,22 +183,6 @@ struct OpFuse {
 };
 #define SRLZ_NO_FUSE OpFuse{nullptr, nullptr, nullptr, 0.f, 0, nullptr}
 
-// Epilogue option of the data-gradient launches whose output is the gradient of a POOLED map (conv2 -> d pooled1, conv3 -> d pooled2;
-// conv64_dgrad_poolsum_kernel<1 / 2>): instead of BatchNorm-forward statistics the tile's partial record receives the two
-// BatchNorm-BACKWARD sums of the block that produced the pooled map,  sum dz  and  sum dz*xhat  with dz = d pooled where pooled > 0
-// (the gradient lives at the window's argmax, and the pooled value IS relu(bn(y)) there: xhat follows from it) — what
-// bn_relu_pool_bwd_reduce computes in a pass of its own over (d pooled, pooled, argmax).  y / argmax are only touched for channels
-// whose BatchNorm scale is exactly 0 (xhat cannot be recovered from the pooled value there).
-struct PoolSum {
-  const float* pooled;    // [N,Hd,Wd,64] like the launch's dst; NULL = off
-  const float* bnp;       // records of the pooled block's BatchNorm (256 floats per group)
-  const float* y;         // raw convolution output under the pooling [N,H,W,64]
-  const uint8_t* argmax;  // [N,Hd,Wd,64]
-  long long y_gstride;    // floats between two groups' images in y
-  int H, W, pad;
-};
-#define SRLZ_NO_POOLSUM PoolSum{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0}
-
 // The records of BatchNorm group `grp` (bnp: 256 floats per group, sums: 128) and the group's slice of the tensors that are
 // indexed like the staged source (y, dy_out): `goff` floats further.
 __device__ __forceinline__ OpFuse fuse_for_group(OpFuse f, int grp, long long goff) {
@@ -222,6 +192,42 @@ __device__ __forceinline__ OpFuse fuse_for_group(OpFuse f, int grp, long long go
   if (f.dy_out) f.dy_out += goff;
   return f;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// The grid walk: position q of ONE BatchNorm group's virtual grid -> image n, grid row a, grid column b (q = (n * PH + a) * PW + b)
+// -> the position's class-(0,0) pixel (y, x) = (a * stride, b * stride) in a tensor of that stride.
+// SHIFTED: q may lie up to one image BEFORE position 0 (the staged range of a padded program starts at min_off < 0): the divisions
+// are done on q + PHW, which stays non-negative, and n is -1 for those positions.
+// Every table builder below and the kernels' destination-side rowinfo go through here.
+// ---------------------------------------------------------------------------------------------------------------
+struct GridPix { int n, y, x; };
+template <bool SHIFTED>
+__device__ __forceinline__ GridPix grid_pix(const ConvProg& P, int q, int stride) {
+  const int qq = SHIFTED ? q + P.PHW : q;
+  const int n1 = fastdiv(qq, P.mPHW, P.sPHW);
+  const int rem = qq - n1 * P.PHW;
+  const int a = fastdiv(rem, P.mPW, P.sPW);
+  const int y = a * stride, x = (rem - a * P.PW) * stride;
+  return GridPix{SHIFTED ? n1 - 1 : n1, y, x};
+}
+
+// Source-side table entry of position q for a source of stride `ss`: pixel index of the position's class-(0,0) source pixel << 4 |
+// bit k: source class k = (cy << 1) | cx is inside the image; 0 = no image (then no class is).  A staging of class k is then, per row:
+// a bit-field extract, an add-shift and an AND (stage_rows_tab, gather_request, plain_request, conv64_wgrad_gather_kernel).
+template <bool SHIFTED>
+__device__ __forceinline__ unsigned src_entry(const ConvProg& P, int q, int ss) {
+  const GridPix g = grid_pix<SHIFTED>(P, q, ss);
+  if (SHIFTED ? (unsigned)g.n < (unsigned)P.N : g.n < P.N) {
+    unsigned f = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) f |= (g.y + (k >> 1) < P.Hs && g.x + (k & 1) < P.Ws) ? 1u << k : 0u;
+    return ((unsigned)((g.n * P.Hs + g.y) * P.Ws + g.x) << 4) | f;
+  }
+  return 0;
+}
+
+// One-pixel table entry of a row inside the tensor: pixel index << 1 | 1 (0 = outside: such a row reads pixel 0 and is dropped)
+__device__ __forceinline__ unsigned pix_entry(int n, int y, int x, int H, int W) { return ((unsigned)((n * H + y) * W + x) << 1) | 1u; }
 
 // Reciprocals of the virtual grid's PH * PW and PW (fastdiv) for rows64_load.
 struct GridDiv { unsigned mPHW, mPW; int sPHW, sPW; };
@@ -245,7 +251,7 @@ __device__ __forceinline__ void stage_rows(float* __restrict__ lds, const float*
   const int cy = cls >> 1, cx = cls & 1;
   const int PHW = PH * PW;
   constexpr int RP = NTHREADS / 16;  // rows per pass
-  // (true divisions: with the uniform divisors hipcc keeps one reciprocal per kernel, and fastdiv here measured 0.5 % SLOWER in
+  // (its own walk, not grid_pix — true divisions: with the uniform divisors hipcc keeps one reciprocal per kernel, and fastdiv here measured 0.5 % SLOWER in
   // conv64_fwd_kernel — unlike in rows64_load, where it is worth 1.5 % of the weight-gradient ring)
   // a pass advances RP grid positions = sn images + sa rows + sb columns (sa < PH, sb < PW): one carry per digit below is then enough
   // on any grid — with sa = RP / PW alone a grid of fewer than RP / PW + 1 rows (maps of a few pixels, several images) carried past
@@ -346,19 +352,7 @@ __host__ __device__ __forceinline__ int rowtab_passes(int nrows) { return ((nrow
 __device__ __forceinline__ void rowtab_build(unsigned* __restrict__ tab, int tpa, const ConvProg& P, int qstart, int nrows) {
   for (int R = threadIdx.x; R < 16 * tpa; R += blockDim.x) {
     unsigned e = 0;
-    if (R < nrows) {
-      const int qq = qstart + R + P.PHW;  // shifted by one image: the first rows of the first tile (negative q) stay non-negative
-      const int n1 = fastdiv(qq, P.mPHW, P.sPHW);
-      const int rem = qq - n1 * P.PHW;
-      const int a = fastdiv(rem, P.mPW, P.sPW);
-      const int y0 = a * P.ss, x0 = (rem - a * P.PW) * P.ss;
-      if ((unsigned)(n1 - 1) < (unsigned)P.N) {
-        unsigned f = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) f |= (y0 + (k >> 1) < P.Hs && x0 + (k & 1) < P.Ws) ? 1u << k : 0u;
-        e = ((unsigned)(((n1 - 1) * P.Hs + y0) * P.Ws + x0) << 4) | f;
-      }
-    }
+    if (R < nrows) e = src_entry<true>(P, qstart + R, P.ss);
     tab[(R & 15) * tpa + (R >> 4)] = e;
   }
 }
@@ -461,11 +455,8 @@ __device__ __forceinline__ void conv64_fwd_body(const float* __restrict__ src, c
     const int q = q0 + tid;
     int ri = -1;
     if (q < P.total_q) {
-      const int n = fastdiv(q, P.mPHW, P.sPHW);
-      const int rem = q - n * P.PHW;
-      const int a = fastdiv(rem, P.mPW, P.sPW);
-      const int ya = a * P.ds, xb = (rem - a * P.PW) * P.ds;
-      if (ya < P.Hd && xb < P.Wd) ri = (((n * P.Hd + ya) * P.Wd + xb) << 2) | (ya + 1 < P.Hd ? 1 : 0) | (xb + 1 < P.Wd ? 2 : 0);
+      const GridPix g = grid_pix<false>(P, q, P.ds);
+      if (g.y < P.Hd && g.x < P.Wd) ri = (((g.n * P.Hd + g.y) * P.Wd + g.x) << 2) | (g.y + 1 < P.Hd ? 1 : 0) | (g.x + 1 < P.Wd ? 2 : 0);
     }
     rowinfo[tid] = ri;
   }
@@ -801,30 +792,19 @@ struct GatherRows {
 
 // The source-side row table of a gather tile (cf. rowtab_build): the walk over (image, row, column), the bounds tests and the pixel
 // offset of a tile's rows were redone by every thread for each of the tile's four classes (~22 vector-ALU instructions per row and
-// class); here the first 192 threads decompose one row each, once per tile:
-//   entry = pixel index of the row's class-(0,0) source pixel << 4 | bit k: class k = (cy << 1) | cx is inside the image  (0 = no row)
+// class); here the first 192 threads decompose one row each, once per tile (src_entry).
 // Layout: row R at (R & 31) * GT_P + (R >> 5): the six rows of thread t (R = (t >> 4) + 32 j) are consecutive words.
-// The tile starts at grid position q0 >= 0 (these programs have min_off == 0).
+// SHIFTED: the staged range [qstart, qstart + nrows) may begin before grid position 0 (qstart >= -PHW: a convolution with padding);
+// the fused backward's programs have min_off == 0 and build it unshifted.
 constexpr int GT_P = 8;
 constexpr int GT_WORDS = GP_RP * GT_P;
-__device__ __forceinline__ void gtab_build(unsigned* __restrict__ tab, const ConvProg& P, int q0, int nrows) {
+template <bool SHIFTED>
+__device__ __forceinline__ void gtab_build(unsigned* __restrict__ tab, const ConvProg& P, int qstart, int nrows) {
   int R = threadIdx.x;
   asm volatile("" : "+v"(R));  // opaque (as in gather_request): the word's address is not worth a register across the tile loop
   if (R < GT_WORDS) {
     unsigned e = 0;
-    if (R < nrows) {
-      const int qq = q0 + R;
-      const int n = fastdiv(qq, P.mPHW, P.sPHW);
-      const int rem = qq - n * P.PHW;
-      const int a = fastdiv(rem, P.mPW, P.sPW);
-      const int y0 = 2 * a, x0 = 2 * (rem - a * P.PW);
-      if (n < P.N) {
-        unsigned f = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) f |= (y0 + (k >> 1) < P.Hs && x0 + (k & 1) < P.Ws) ? 1u << k : 0u;
-        e = ((unsigned)((n * P.Hs + y0) * P.Ws + x0) << 4) | f;
-      }
-    }
+    if (R < nrows) e = src_entry<SHIFTED>(P, qstart + R, 2);
     tab[(R & (GP_RP - 1)) * GT_P + (R >> 5)] = e;
   }
 }
@@ -859,13 +839,7 @@ __device__ __forceinline__ void gather_request(GatherRows& r, const float* __res
   r.ok = okmask;
 }
 
-// A buffer resource over `bytes` bytes at `p` (raw, unstrided): buffer stores whose offset lies outside are DROPPED by the hardware,
-// which makes a conditional store branch-free (offset = GP_DROP for a lane that must not write).  That matters beyond the branch
-// itself: vmcnt counts stores too and is in-order, and behind a store inside a branch hipcc can only wait for everything, so
-// every later "wait for the weight slab" would also wait for these stores' HBM round trip.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t gp_buffer(float* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(p, 0, (int)bytes, 0x00020000);
-}
+// Branch-free conditional stores through a buffer resource (common.h: raw_buffer): offset = GP_DROP for a lane that must not write.
 constexpr unsigned GP_DROP = 0xFFFFFF00u;
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -876,7 +850,7 @@ constexpr unsigned GP_DROP = 0xFFFFFF00u;
 // persistent workgroups (2 per CU) walk their XCD's tiles, class c + 1 is requested behind the barrier that opens class c and lands
 // behind its last tap, class 0 of the next tile travels under the single tap of class 3 and the epilogue; branch-free requests and
 // stores.  Differences: no BatchNorm-backward rebuild, no dy_out; the programs of a convolution with padding start their staged range
-// at a NEGATIVE grid offset (min_off < 0: the row table is built with rowtab_build's one-image shift); the epilogue takes the
+// at a NEGATIVE grid offset (min_off < 0: the row table is built SHIFTED); the epilogue takes the
 // per-tile BatchNorm partial sums (sum y, sum y^2 over the tile's valid rows) like conv64_fwd_kernel's, in this kernel's own
 // (fixed) summation order.  Same tiles, same accumulation order of the contraction: y is bit-identical to conv64_fwd_kernel's.
 // ---------------------------------------------------------------------------------------------------------------
@@ -884,29 +858,6 @@ struct PlainRows {
   f32x4 v[GP_BATCH];
   unsigned ok;
 };
-
-// gtab_build for a staged range [qstart, qstart + nrows) that may begin before grid position 0 (qstart >= -PHW)
-__device__ __forceinline__ void gtab_build_shifted(unsigned* __restrict__ tab, const ConvProg& P, int qstart, int nrows) {
-  int R = threadIdx.x;
-  asm volatile("" : "+v"(R));
-  if (R < GT_WORDS) {
-    unsigned e = 0;
-    if (R < nrows) {
-      const int qq = qstart + R + P.PHW;  // shifted by one image: stays non-negative
-      const int n1 = fastdiv(qq, P.mPHW, P.sPHW);
-      const int rem = qq - n1 * P.PHW;
-      const int a = fastdiv(rem, P.mPW, P.sPW);
-      const int y0 = 2 * a, x0 = 2 * (rem - a * P.PW);
-      if ((unsigned)(n1 - 1) < (unsigned)P.N) {
-        unsigned f = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) f |= (y0 + (k >> 1) < P.Hs && x0 + (k & 1) < P.Ws) ? 1u << k : 0u;
-        e = ((unsigned)(((n1 - 1) * P.Hs + y0) * P.Ws + x0) << 4) | f;
-      }
-    }
-    tab[(R & (GP_RP - 1)) * GT_P + (R >> 5)] = e;
-  }
-}
 
 __device__ __forceinline__ void plain_request(PlainRows& r, const float* __restrict__ src, const unsigned* __restrict__ tab, int cls,
                                               int W) {
@@ -980,7 +931,7 @@ __global__ __launch_bounds__(GP_THREADS, 4) void conv64_gather_pipe_kernel(const
     const int tile = tbase + k;
     const int grp = (P.G > 1 && tile >= P.tpg) ? 1 : 0;  // (G <= 2, checked by the host)
     const int q0 = (tile - grp * P.tpg) * TM;
-    gtab_build_shifted(gtab, P, q0 + P.min_off, nrows);
+    gtab_build<true>(gtab, P, q0 + P.min_off, nrows);
     __syncthreads();
     plain_request(rr, src_all + grp * P.src_gstride, gtab, cls0, P.Ws);
     plain_land(As, rr, nrows);
@@ -990,7 +941,7 @@ __global__ __launch_bounds__(GP_THREADS, 4) void conv64_gather_pipe_kernel(const
     const int grp = (P.G > 1 && tile >= P.tpg) ? 1 : 0;
     const int q0 = (tile - grp * P.tpg) * TM;
     const float* __restrict__ src = src_all + grp * P.src_gstride;
-    const __amdgpu_buffer_rsrc_t dst = gp_buffer(dst_all + grp * P.dst_gstride, dst_bytes);
+    const __amdgpu_buffer_rsrc_t dst = raw_buffer(dst_all + grp * P.dst_gstride, dst_bytes);
     const int k2 = k + wpx;  // this workgroup's next tile (past the end: this one again, with no rows)
     const int tile2 = tbase + (k2 < tcnt ? k2 : k);
     const int grp2 = (P.G > 1 && tile2 >= P.tpg) ? 1 : 0;
@@ -1000,11 +951,8 @@ __global__ __launch_bounds__(GP_THREADS, 4) void conv64_gather_pipe_kernel(const
       const int q = q0 + tid;
       int n = -1, ya = 0, xb = 0;
       if (q < P.total_q) {
-        n = fastdiv(q, P.mPHW, P.sPHW);
-        const int rem = q - n * P.PHW;
-        const int a = fastdiv(rem, P.mPW, P.sPW);
-        ya = a * P.ds;
-        xb = (rem - a * P.PW) * P.ds;
+        const GridPix g = grid_pix<false>(P, q, P.ds);
+        n = g.n; ya = g.y; xb = g.x;
       }
       ri[tid] = n; ri[TM + tid] = ya; ri[2 * TM + tid] = xb;
     }
@@ -1036,7 +984,7 @@ __global__ __launch_bounds__(GP_THREADS, 4) void conv64_gather_pipe_kernel(const
         for (int i = 0; i < BV; ++i) breg[i] = wsrc[bslot_t + i * 64];
       }
       if (ti == 4 || ti == 6 || ti == 8) plain_land(As, rr, nrows);
-      if (ti == 7) gtab_build_shifted(gtab, P, q02 + P.min_off, k2 < tcnt ? nrows : 0);
+      if (ti == 7) gtab_build<true>(gtab, P, q02 + P.min_off, k2 < tcnt ? nrows : 0);
       __syncthreads();
       if (ti == 0) plain_request(rr, src, gtab, cls1, P.Ws);
       if (ti == 4) plain_request(rr, src, gtab, cls2, P.Ws);
@@ -1184,13 +1132,9 @@ __device__ __forceinline__ void ytab_build(unsigned* __restrict__ tab, const Con
   int R = (int)threadIdx.x - 256;
   asm volatile("" : "+v"(R));
   if ((unsigned)R < (unsigned)YT_WORDS) {
-    const int qq = q0 + R;
-    const int n = fastdiv(qq, P.mPHW, P.sPHW);
-    const int rem = qq - n * P.PHW;
-    const int a = fastdiv(rem, P.mPW, P.sPW);
-    const int b = rem - a * P.PW;
-    const bool ok = live && n < P.N && a < P.Hd && b < P.Wd;
-    tab[((R >> 5) * 8 + (R & 7)) * 4 + ((R >> 3) & 3)] = ok ? ((unsigned)((n * P.Hd + a) * P.Wd + b) << 1) | 1u : 0u;
+    const GridPix g = grid_pix<false>(P, q0 + R, 1);
+    const bool ok = live && g.n < P.N && g.y < P.Hd && g.x < P.Wd;
+    tab[((R >> 5) * 8 + (R & 7)) * 4 + ((R >> 3) & 3)] = ok ? pix_entry(g.n, g.y, g.x, P.Hd, P.Wd) : 0u;
   }
 }
 
@@ -1360,7 +1304,7 @@ __global__ __launch_bounds__(GP_THREADS, 2) void conv64_bwd_fused_kernel(const f
     for (int i = 0; i < BV; ++i) breg[i] = wsrc[wave * (BV * 64) + lane + i * 64];
   }
   const unsigned dst_bytes = (unsigned)P.dst_gstride * 4u;
-  const __amdgpu_buffer_rsrc_t bnbuf = gp_buffer(fb.bnpart, fb.bnpart ? (unsigned)(P.G * fb.bn_rows) * 512u : 0u);
+  const __amdgpu_buffer_rsrc_t bnbuf = raw_buffer(fb.bnpart, fb.bnpart ? (unsigned)(P.G * fb.bn_rows) * 512u : 0u);
 
   f32x16 aw0[2], aw1[1], aw2[1], aw3[1];  // weight-gradient accumulators of the four classes
 #pragma unroll
@@ -1375,7 +1319,7 @@ __global__ __launch_bounds__(GP_THREADS, 2) void conv64_bwd_fused_kernel(const f
     const int tile = tbase + k;
     const int grp = (P.G > 1 && tile >= P.tpg) ? 1 : 0;
     const int q0 = (tile - grp * P.tpg) * TM;
-    gtab_build(gtab, P, q0, nrows);
+    gtab_build<false>(gtab, P, q0, nrows);
     ytab_build(ytab, P, q0, true);
     __syncthreads();  // the tables, frec and xrec are complete
     gather_request(rr, src_all + grp * P.src_gstride, fuse_all.y + grp * P.src_gstride, gtab, cls0, P.Ws);
@@ -1402,7 +1346,7 @@ __global__ __launch_bounds__(GP_THREADS, 2) void conv64_bwd_fused_kernel(const f
     const int q0 = (tile - grp * P.tpg) * TM;
     const float* __restrict__ src = src_all + grp * P.src_gstride;
     const float* __restrict__ ysrc = fuse_all.y + grp * P.src_gstride;
-    const __amdgpu_buffer_rsrc_t dst = gp_buffer(dst_all + grp * P.dst_gstride, dst_bytes);
+    const __amdgpu_buffer_rsrc_t dst = raw_buffer(dst_all + grp * P.dst_gstride, dst_bytes);
     const float* lrec = frec + grp * 256;
     const int k2 = k + wpx;
     const bool more = k2 < tcnt;
@@ -1413,7 +1357,8 @@ __global__ __launch_bounds__(GP_THREADS, 2) void conv64_bwd_fused_kernel(const f
     if (tid < TM) {
       const int q = q0 + tid;
       int n = -1, ya = 0, xb = 0;
-      if (q < P.total_q) {
+      if (q < P.total_q) {  // (grid_pix written out: through the helper hipcc orders this kernel's scalar loads differently — three
+        // instructions more in a kernel at its register limit; the generated code is kept as it was)
         n = fastdiv(q, P.mPHW, P.sPHW);
         const int rem = q - n * P.PHW;
         const int a = fastdiv(rem, P.mPW, P.sPW);
@@ -1465,7 +1410,7 @@ __global__ __launch_bounds__(GP_THREADS, 2) void conv64_bwd_fused_kernel(const f
                                                                              // run-time branch around a landing, or its join costs a full vmcnt(0))
       // the NEXT tile's row tables, between the last request of this tile (tap 4) and the first of the next (tap 6) — the barriers of
       // taps 5 and 6 fence both sides; past the end: no rows -> every entry 0 -> every row reads pixel 0 and is dropped
-      if (ti == 5) { gtab_build(gtab, P, q02, more ? nrows : 0); ytab_build(ytab, P, q02, more); }
+      if (ti == 5) { gtab_build<false>(gtab, P, q02, more ? nrows : 0); ytab_build(ytab, P, q02, more); }
       if (ti == 0) gather_request<FB_NJ1>(rr, src, ysrc, gtab, cls1, P.Ws);
       if (ti == 2) gather_request(rr, src, ysrc, gtab, cls2, P.Ws);
       if (ti == 4) gather_request<FB_NJ3>(rr, src, ysrc, gtab, cls3, P.Ws);
@@ -1569,7 +1514,7 @@ __global__ __launch_bounds__(GP_THREADS, 2) void conv64_bwd_fused_kernel(const f
   __syncthreads();  // (everything in LDS is dead from here on)
   {
     const int h = lane >> 5, l31 = lane & 31;
-    float* out = fb.wpartial + (size_t)blockIdx.x * (NTAPS * 4096 + 64);
+    float* out = fb.wpartial + (size_t)blockIdx.x * WGRAD_PARTIAL_FLOATS;
     auto put = [&](const f32x16& a, int tap, int mi, int nj) {
       float* o = out + (size_t)P.tw[tap] * 4096;
 #pragma unroll
@@ -1750,7 +1695,7 @@ __global__ __launch_bounds__(256, 2) void conv64_wgrad_kernel(const float* __res
 //    chunk in the inter-barrier section of the last group, when nobody reads them.
 // Same chunks per workgroup, same MFMA order, same partial layout as conv64_wgrad_kernel<true, 64>: results are bit-identical.
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int WG_TK = 64;           // positions per chunk
+constexpr int WG_TK = 64;           // positions per chunk (128 was tried: the extra staging registers spill)
 constexpr int WG_SROWS = 8;         // source rows per thread: WG_TK + span <= 128
 constexpr int WG_SWORDS = 16 * WG_SROWS, WG_GWORDS = 16 * 4;
 
@@ -1762,11 +1707,8 @@ __device__ __forceinline__ void wg_gtab_build(unsigned* __restrict__ tab, const 
     const int q = q0 + R;
     unsigned e = 0;
     if (q < P.total_q) {
-      const int n = fastdiv(q, P.mPHW, P.sPHW);
-      const int rem = q - n * P.PHW;
-      const int a = fastdiv(rem, P.mPW, P.sPW);
-      const int ya = a * P.ds, xb = (rem - a * P.PW) * P.ds;
-      if (ya < P.Hd && xb < P.Wd) e = ((unsigned)((n * P.Hd + ya) * P.Wd + xb) << 1) | 1u;
+      const GridPix g = grid_pix<false>(P, q, P.ds);
+      if (g.y < P.Hd && g.x < P.Wd) e = pix_entry(g.n, g.y, g.x, P.Hd, P.Wd);
     }
     tab[(R & 15) * 4 + (R >> 4)] = e;
   }
@@ -1941,7 +1883,6 @@ __global__ __launch_bounds__(256, 2) void conv64_wgrad_gather_kernel(const float
 // slots, "& 255" on every address — cost three VALU instructions and one ds_read_b32 per MFMA, and that instruction stream,
 // not the matrix pipe, bounded the loop: 113 TF with every load and barrier removed.)
 // RING_ROWS >= TK + span + TK (the prefetched TK rows are written only after the readers' barrier).
-template <int V> struct IntC { static constexpr int value = V; };
 constexpr int RING_ROWS = 246, RING_MIRROR = 8, RING = RING_ROWS + RING_MIRROR;  // (246 + 8 + 64 rows + 2 rows of tables = 80 KB)
 // the stride-2 (ConvTranspose) kernel walks 32-position chunks: RING_ROWS_S2 >= 32 + span + 32, and 4 x 32 gradient rows next to it
 constexpr int RING_ROWS_S2 = 184, RING_S2 = RING_ROWS_S2 + RING_MIRROR;
@@ -2022,13 +1963,15 @@ __device__ __forceinline__ void rows64_store(float* __restrict__ lds, int rbase,
 // pixel index << 1 | 1, 0 = outside the tensor.  One wave builds one table (lane = row).
 __device__ __forceinline__ void ring_tab_build(unsigned* __restrict__ tab, const ConvProg& P, int H, int W, int stride, int cls,
                                                int qstart, int R) {
+  // (the walk of grid_pix<true> written out: this kernel scales by a shift — stride is 1 or 2 — where grid_pix multiplies, and through
+  // the helper its generated code changes; rows64_load keeps its own incremental walk for the same reason)
   const int qq = qstart + R + P.PHW;  // shifted by one image: non-negative for the first rows of the first chunk
   const int n1 = fastdiv(qq, P.mPHW, P.sPHW);
   const int rem = qq - n1 * P.PHW;
   const int a = fastdiv(rem, P.mPW, P.sPW);
   const int y = (a << (stride - 1)) + (cls >> 1), x = ((rem - a * P.PW) << (stride - 1)) + (cls & 1);
   const bool ok = (unsigned)(n1 - 1) < (unsigned)P.N && y < H && x < W;
-  tab[(R & 15) * 4 + (R >> 4)] = ok ? ((unsigned)(((n1 - 1) * H + y) * W + x) << 1) | 1u : 0u;
+  tab[(R & 15) * 4 + (R >> 4)] = ok ? pix_entry(n1 - 1, y, x, H, W) : 0u;
 }
 
 // rows64_load through such a table (same loads, same zeros for rows outside)
@@ -2385,13 +2328,12 @@ static int check_desc(const srlz_conv64_desc* d) {
   return 0;
 }
 
-static int program_for(ConvProg* P, const srlz_conv64_desc* d, int backward_data) {
-  int rc;
+// What every entry point that takes a descriptor begins with: check_desc, then the descriptor's forward or data-gradient program
+static int with_program(const srlz_conv64_desc* d, int backward_data, ConvProg* P) {
+  if (int rc = check_desc(d)) return rc;
   const int G = d->groups > 1 ? d->groups : 1;
-  if (!backward_data)
-    rc = build_program(P, !d->transposed, d->stride, d->pad, d->n, d->hi, d->wi, d->ho, d->wo, G);
-  else
-    rc = build_program(P, d->transposed, d->stride, d->pad, d->n, d->ho, d->wo, d->hi, d->wi, G);
+  const int rc = backward_data ? build_program(P, d->transposed, d->stride, d->pad, d->n, d->ho, d->wo, d->hi, d->wi, G)
+                               : build_program(P, !d->transposed, d->stride, d->pad, d->n, d->hi, d->wi, d->ho, d->wo, G);
   SRLZ_REQUIRE(rc == 0, SRLZ_ERR_BAD_DESC, "conv64: cannot build a grid program for this descriptor");
   return 0;
 }
@@ -2403,8 +2345,29 @@ static size_t fwd_lds_bytes(const ConvProg& P) {  // source rows, slab, row tabl
 static size_t convn_lds_bytes(const ConvProg& P) {
   return (size_t)(TM + P.span) * 256 + 16384 + (size_t)64 * rowtab_passes(TM + P.span) + TM * 4 + 8 * 128 * 4;
 }
-static size_t wgrad_lds_bytes(const ConvProg& P, int tk) { return (size_t)(tk + P.span + tk) * 256; }
-static int wgrad_tk(const ConvProg& P) { (void)P; return 64; }  // 128 was tried: the extra staging registers spill
+static size_t wgrad_lds_bytes(const ConvProg& P) { return (size_t)(WG_TK + P.span + WG_TK) * 256; }
+
+// ---- Which kernel takes this program ----
+// A stride-2 gather program as the pipelined kernels expect it: four source classes in tap groups {4, 2, 2, 1} (taps 0-3, 4-5, 6-7, 8),
+// one destination class (conv3's forward, a ConvTranspose's data gradient); never under an ablation switch.
+static bool taps_grouped_4221(const ConvProg& P) {
+  bool grouped = P.s2 && P.ss == 2 && !P.dbg;
+  for (int t = 0; t < NTAPS; ++t) grouped = grouped && P.tsrc[t] == P.tsrc[t < 4 ? 0 : t < 6 ? 4 : t < 8 ? 6 : 8] && P.tdst[t] == 0;
+  return grouped;
+}
+
+// The 32-bit limits (all per BatchNorm group: P.N images).
+// byte offsets into buffer resources over one group's src / dst, with room below the DROP offset of a lane that must not store
+static bool fits_32bit_buffer_bytes(const ConvProg& P) {
+  return P.src_gstride * 4 < (1LL << 32) - 65536 && P.dst_gstride * 4 < (1LL << 32) - 65536;
+}
+// float offsets of the stagings and row tables into one group's src / dst
+static bool fits_32bit_src_floats(const ConvProg& P) { return (long long)P.N * P.Hs * P.Ws * 64 < (1LL << 32); }
+static bool fits_32bit_dst_floats(const ConvProg& P) { return (long long)P.N * P.Hd * P.Wd * 64 < (1LL << 32); }
+// the destination word of a forward tile (rowinfo): pixel index << 2 | two bits, negative = outside
+static bool fits_32bit_dst_rowinfo(const ConvProg& P) { return (long long)P.N * P.Hd * P.Wd < (1LL << 29); }
+// fastdiv takes dividends below 2^31: the last grid position + the one-image shift + how far a kernel stages past it
+static bool fits_31bit_grid(const ConvProg& P, int reach) { return (long long)P.total_q + P.PHW + reach < (1LL << 31); }
 
 // conv64_gather_pipe_kernel takes a program when it is a stride-2 gather with the tap groups {4, 2, 2, 1}, at most two BatchNorm groups,
 // a staged class of at most 192 rows (PW <= 63), 32-bit byte offsets — and at least 256 tiles PER BatchNorm GROUP: the pipeline pays
@@ -2415,10 +2378,41 @@ static int wgrad_tk(const ConvProg& P) { (void)P; return 64; }  // 128 was tried
 constexpr int GATHER_PIPE_MIN_TILES_PER_GROUP = 256;
 static bool gather_pipe_ok(const ConvProg& P) {
   if (P.tpg < GATHER_PIPE_MIN_TILES_PER_GROUP) return false;
-  bool grouped = P.s2 && P.ss == 2 && P.G <= 2 && !P.dbg;
-  for (int t = 0; t < NTAPS; ++t) grouped = grouped && P.tsrc[t] == P.tsrc[t < 4 ? 0 : t < 6 ? 4 : t < 8 ? 6 : 8] && P.tdst[t] == 0;
-  const bool fits32 = P.src_gstride * 4 < (1LL << 32) - 65536 && P.dst_gstride * 4 < (1LL << 32) - 65536;
-  return grouped && fits32 && TM + P.span <= GP_RP * GP_BATCH && GP_RP <= P.PHW && -P.min_off <= P.PHW;
+  return taps_grouped_4221(P) && P.G <= 2 && fits_32bit_buffer_bytes(P) && TM + P.span <= GP_RP * GP_BATCH && GP_RP <= P.PHW &&
+         -P.min_off <= P.PHW;
+}
+
+// conv64_bwd_fused_kernel: the same programs without padding (min_off == 0), and at least 8 tiles
+static bool fused_bwd_ok(const ConvProg& P) {
+  // the second and fourth class are requested and landed for the rows their taps can reach only (FB_NJ1 / FB_NJ3); they share the
+  // short LDS buffer As1 (TM + FB_REACH1 rows)
+  const bool reach = P.toff[4] >= 0 && P.toff[5] >= 0 && P.toff[4] < FB_REACH1 && P.toff[5] < FB_REACH1 && P.toff[8] >= 0 &&
+                     P.toff[8] <= FB_REACH3;
+  return taps_grouped_4221(P) && P.G <= 2 && P.min_off == 0 && fits_32bit_buffer_bytes(P) && reach &&
+         TM + P.span <= GP_RP * GP_BATCH && GP_RP <= P.PHW && P.G * P.tpg >= 8;
+}
+
+// The weight gradient is a chain of SHAPE fallbacks (no environment switches):
+//   ring_s2  ConvTranspose programs (one source class, taps {4, 2, 2, 1} by destination class) whose span fits the 184-row ring
+//            (PW <= 119): conv64_wgrad_ring_s2_kernel, 32-position chunks carrying all four destination classes;
+//   ring     stride-1 programs whose span fits the 246-row ring (PW <= 58), with the 32-bit offsets of its row tables:
+//            conv64_wgrad_ring_kernel;
+//   gather   stride-2 gather programs (conv3) with a plain source, chunk + halo within a thread's registers, 32-bit offsets:
+//            conv64_wgrad_gather_kernel (same grid, same partials as conv64_wgrad_kernel<true, 64>);
+//   chunk    anything else (wider images, a gradient rebuilt from (dA, y)): the chunk-at-a-time conv64_wgrad_kernel.
+// x_bnp: the source is relu(bn(x)); dy_bn_y: the gradient is rebuilt from (dA, y) (srlz_bn_bwd_operand).
+enum class WgradRoute { ring_s2, ring, gather, chunk };
+static WgradRoute wgrad_route(const ConvProg& P, const float* x_bnp, const float* dy_bn_y) {
+  bool single_src = true;
+  for (int t = 1; t < NTAPS; ++t) single_src = single_src && P.tsrc[t] == P.tsrc[0];
+  if (single_src && !dy_bn_y && P.s2 && 32 + P.span + 32 <= RING_ROWS_S2) return WgradRoute::ring_s2;
+  if (single_src && !dy_bn_y && !P.s2 && WG_TK + P.span + WG_TK <= RING_ROWS && fits_32bit_src_floats(P) && fits_32bit_dst_floats(P) &&
+      fits_31bit_grid(P, P.PHW))
+    return WgradRoute::ring;
+  if (taps_grouped_4221(P) && WG_TK + P.span <= 16 * WG_SROWS && fits_32bit_src_floats(P) && fits_32bit_dst_floats(P) &&
+      fits_31bit_grid(P, WG_TK + P.span) && !x_bnp && !dy_bn_y)
+    return WgradRoute::gather;
+  return WgradRoute::chunk;
 }
 
 static int launch_fwd(const float* src, const float* wpack, const float* bias, float* dst, float* stats,
@@ -2427,9 +2421,7 @@ static int launch_fwd(const float* src, const float* wpack, const float* bias, f
   const size_t lds = fwd_lds_bytes(P);
   SRLZ_REQUIRE(lds <= 160 * 1024, SRLZ_ERR_BAD_DESC, "conv64: tile needs %zu bytes of LDS", lds);
   // the row table keeps pixel indices in 28 bits and the staging 32-bit float offsets; the fast divisions take dividends below 2^31
-  SRLZ_REQUIRE((long long)P.N * P.Hs * P.Ws * 64 < (1LL << 32) && (long long)P.N * P.Hd * P.Wd < (1LL << 29) &&
-                   (long long)P.total_q + P.PHW + TM + P.span < (1LL << 31),
-               SRLZ_ERR_BAD_DESC, "conv64: a group of %d images of %d x %d -> %d x %d is beyond the tile tables' 32-bit offsets", P.N, P.Hs,
+  SRLZ_REQUIRE(fits_32bit_src_floats(P) && fits_32bit_dst_rowinfo(P) && fits_31bit_grid(P, TM + P.span), SRLZ_ERR_BAD_DESC, "conv64: a group of %d images of %d x %d -> %d x %d is beyond the tile tables' 32-bit offsets", P.N, P.Hs,
                P.Ws, P.Hd, P.Wd);
   if (psum) {  // data gradient whose epilogue takes the pooled block's BatchNorm-backward sums (its own instantiation)
     SRLZ_REQUIRE(!src_fuse.y && !src_fuse.bnp && stats && !bias, SRLZ_ERR_BAD_DESC, "conv64: the pooled-block epilogue takes a plain operand");
@@ -2453,7 +2445,7 @@ static int launch_fwd(const float* src, const float* wpack, const float* bias, f
                 P, ntiles, src_fuse);                                                                                      \
   } while (0)
   if (src_fuse.y) {
-    SRLZ_REQUIRE((long long)P.N * P.Hs * P.Ws * 64 < (1LL << 32), SRLZ_ERR_BAD_DESC,
+    SRLZ_REQUIRE(fits_32bit_src_floats(P), SRLZ_ERR_BAD_DESC,
                  "conv64: a group's operand has %lld floats (the fused staging keeps 32-bit row offsets)", (long long)P.N * P.Hs * P.Ws * 64);
     // (a fused BatchNorm-backward operand that must also be STORED for a separate weight-gradient launch: the shapes
     // conv64_bwd_fused_kernel does not take — fewer than 8 tiles, a low-resolution grid wider than 63)
@@ -2489,18 +2481,8 @@ static int make_bwd_fuse(OpFuse* f, const srlz_bn_bwd_operand* o, const char* wh
 }
 
 // workgroups of the weight-gradient kernels (all groups together); a multiple of P.G
-// conv64_wgrad_gather_kernel: four source classes in tap groups {4, 2, 2, 1}, one destination class, chunk + halo within its registers,
-// 32-bit offsets
-static bool wgrad_gather_ok(const ConvProg& P) {
-  bool grouped = P.s2 && P.ss == 2 && !P.dbg;
-  for (int t = 0; t < NTAPS; ++t) grouped = grouped && P.tsrc[t] == P.tsrc[t < 4 ? 0 : t < 6 ? 4 : t < 8 ? 6 : 8] && P.tdst[t] == 0;
-  return grouped && WG_TK + P.span <= 16 * WG_SROWS && (long long)P.N * P.Hs * P.Ws * 64 < (1LL << 32) &&
-         (long long)P.N * P.Hd * P.Wd * 64 < (1LL << 32) && (long long)P.total_q + P.PHW + WG_TK + P.span < (1LL << 31);
-}
-
 static int wgrad_grid(const ConvProg& P) {
-  const int tk = wgrad_tk(P);
-  const int nchunks = (P.total_q + tk - 1) / tk;  // per group
+  const int nchunks = (P.total_q + WG_TK - 1) / WG_TK;  // per group
   int g = 2 * srlz_device_cus() / P.G;           // two persistent workgroups per CU; per group
   // (Fewer, longer-running workgroups on the small layers — at least 8 chunks each, to halve the 147 KB partial every workgroup
   // leaves for the second stage — were measured in round 4 and lost: conv3's weight gradient 121 -> 172 us, ConvT1's 31 -> 102 us,
@@ -2559,11 +2541,8 @@ __global__ __launch_bounds__(256, 2) void convN_fwd_kernel(const float* __restri
     const int q = q0 + tid;
     int ri = -1;
     if (q < P.total_q) {
-      const int n = fastdiv(q, P.mPHW, P.sPHW);
-      const int rem = q - n * P.PHW;
-      const int a = fastdiv(rem, P.mPW, P.sPW);
-      const int ya = a * P.ds, xb = (rem - a * P.PW) * P.ds;
-      if (ya < P.Hd && xb < P.Wd) ri = (n * P.Hd + ya) * P.Wd + xb;
+      const GridPix g = grid_pix<false>(P, q, P.ds);
+      if (g.y < P.Hd && g.x < P.Wd) ri = (g.n * P.Hd + g.y) * P.Wd + g.x;
     }
     rowinfo[tid] = ri;
   }
@@ -2793,37 +2772,33 @@ extern "C" int srlz_conv64_pack_weights(const float* w_ref, float* wpack_fwd, fl
 }
 
 extern "C" int srlz_conv64_fwd_tiles(const srlz_conv64_desc* d) {
-  if (check_desc(d)) return -1;
   ConvProg P;
-  if (program_for(&P, d, 0)) return -1;
+  if (with_program(d, 0, &P)) return -1;
   return P.G * P.tpg;
 }
 
 extern "C" int srlz_conv64_fwd(const float* x, const float* wpack_fwd, const float* bias, float* y,
                                float* stats_partial, const float* x_bnp, const srlz_conv64_desc* d,
                                srlz_stream_t stream) {
-  if (int rc = check_desc(d)) return rc;
-  SRLZ_REQUIRE(x && wpack_fwd && y, SRLZ_ERR_NULL, "conv64_fwd: null pointer");
   ConvProg P;
-  if (int rc = program_for(&P, d, 0)) return rc;
+  if (int rc = with_program(d, 0, &P)) return rc;
+  SRLZ_REQUIRE(x && wpack_fwd && y, SRLZ_ERR_NULL, "conv64_fwd: null pointer");
   return launch_fwd(x, wpack_fwd, bias, y, stats_partial, P, as_stream(stream), OpFuse{x_bnp, nullptr, nullptr, 0.f, 0, nullptr});
 }
 
 extern "C" int srlz_conv64_bwd_data(const float* dy, const float* wpack_bwd, float* dx, const srlz_bn_bwd_operand* dy_bn,
                                     const srlz_conv64_desc* d, srlz_stream_t stream) {
-  if (int rc = check_desc(d)) return rc;
-  SRLZ_REQUIRE(dy && wpack_bwd && dx, SRLZ_ERR_NULL, "conv64_bwd_data: null pointer");
   ConvProg P;
-  if (int rc = program_for(&P, d, 1)) return rc;
+  if (int rc = with_program(d, 1, &P)) return rc;
+  SRLZ_REQUIRE(dy && wpack_bwd && dx, SRLZ_ERR_NULL, "conv64_bwd_data: null pointer");
   OpFuse gf;
   if (int rc = make_bwd_fuse(&gf, dy_bn, "conv64_bwd_data")) return rc;
   return launch_fwd(dy, wpack_bwd, nullptr, dx, nullptr, P, as_stream(stream), gf);
 }
 
 extern "C" int srlz_conv64_bwd_data_tiles(const srlz_conv64_desc* d) {
-  if (check_desc(d)) return -1;
   ConvProg P;
-  if (program_for(&P, d, 1)) return -1;
+  if (with_program(d, 1, &P)) return -1;
   return P.G * P.tpg;
 }
 
@@ -2831,7 +2806,8 @@ extern "C" int srlz_conv64_bwd_data_pool_sums(const float* dy, const float* wpac
                                               const float* pool_bnp, const float* pool_y, const uint8_t* pool_argmax,
                                               const srlz_pool_desc* pd, float* bn_bwd_partial, const srlz_conv64_desc* d,
                                               srlz_stream_t stream) {
-  if (int rc = check_desc(d)) return rc;
+  ConvProg P;
+  if (int rc = with_program(d, 1, &P)) return rc;
   SRLZ_REQUIRE(dy && wpack_bwd && dx && pooled && pool_bnp && pool_y && pool_argmax && pd && bn_bwd_partial, SRLZ_ERR_NULL,
                "conv64_bwd_data_pool_sums: null pointer");
   // dx (this layer's input gradient) is the gradient of the pooled map pd describes: same images, same spatial size, NHWC
@@ -2839,84 +2815,77 @@ extern "C" int srlz_conv64_bwd_data_pool_sums(const float* dy, const float* wpac
                (pd->groups > 1 ? pd->groups : 1) == (d->groups > 1 ? d->groups : 1), SRLZ_ERR_BAD_DESC,
                "conv64_bwd_data_pool_sums: the pooled map [%d,%d,%d] is not this layer's input [%d,%d,%d]", pd->n, pd->hp, pd->wp, d->n,
                d->hi, d->wi);
-  ConvProg P;
-  if (int rc = program_for(&P, d, 1)) return rc;
   const int G = d->groups > 1 ? d->groups : 1;
   PoolSum ps = {pooled, pool_bnp, pool_y, pool_argmax, (long long)(pd->n / G) * pd->h * pd->w * 64, pd->h, pd->w, pd->pool_pad};
   return launch_fwd(dy, wpack_bwd, nullptr, dx, bn_bwd_partial, P, as_stream(stream), SRLZ_NO_FUSE, &ps);
 }
 
 extern "C" size_t srlz_conv64_bwd_weight_workspace(const srlz_conv64_desc* d) {
-  if (check_desc(d)) return 0;
   ConvProg P;
-  if (program_for(&P, d, 0)) return 0;
-  return (size_t)wgrad_grid(P) * (NTAPS * 4096 + 64) * sizeof(float);
+  if (with_program(d, 0, &P)) return 0;
+  return (size_t)wgrad_grid(P) * WGRAD_PARTIAL_FLOATS * sizeof(float);
 }
 
 extern "C" int srlz_conv64_bwd_weight(const float* x, const float* dy, float* dw_ref, float* dbias, const float* x_bnp,
                                       const srlz_bn_bwd_operand* dy_bn, void* ws, size_t ws_bytes,
                                       const srlz_conv64_desc* d, srlz_stream_t stream) {
-  if (int rc = check_desc(d)) return rc;
+  ConvProg P;
+  if (int rc = with_program(d, 0, &P)) return rc;
   OpFuse gf;
   if (int rc = make_bwd_fuse(&gf, dy_bn, "conv64_bwd_weight")) return rc;
   SRLZ_REQUIRE(gf.dy_out == nullptr, SRLZ_ERR_BAD_DESC, "conv64_bwd_weight: dy_out is only produced by srlz_conv64_bwd_data");
   const OpFuse xf = OpFuse{x_bnp, nullptr, nullptr, 0.f, 0, nullptr};
   SRLZ_REQUIRE(x && dy && dw_ref && ws, SRLZ_ERR_NULL, "conv64_bwd_weight: null pointer");
-  ConvProg P;
-  if (int rc = program_for(&P, d, 0)) return rc;
   const int grid = wgrad_grid(P);
-  SRLZ_REQUIRE(ws_bytes >= (size_t)grid * (NTAPS * 4096 + 64) * sizeof(float), SRLZ_ERR_WORKSPACE,
+  SRLZ_REQUIRE(ws_bytes >= (size_t)grid * WGRAD_PARTIAL_FLOATS * sizeof(float), SRLZ_ERR_WORKSPACE,
                "conv64_bwd_weight: workspace too small (%zu bytes)", ws_bytes);
-  const int tk = wgrad_tk(P);
-  const int nchunks = (P.total_q + tk - 1) / tk;  // per BatchNorm group
+  const int nchunks = (P.total_q + WG_TK - 1) / WG_TK;  // per BatchNorm group
   hipStream_t st = as_stream(stream);
   float* partial = (float*)ws;
-  bool single_src = true;
-  for (int t = 1; t < NTAPS; ++t) single_src = single_src && P.tsrc[t] == P.tsrc[0];
-  int launched_grid = grid;
-  // The chain below is a chain of SHAPE fallbacks (no environment switches): ConvTranspose programs whose span fits the 184-row ring
-  // (PW <= 119) -> conv64_wgrad_ring_s2_kernel; stride-1 programs whose span fits the 246-row ring (PW <= 58) with 32-bit offsets ->
-  // conv64_wgrad_ring_kernel; stride-2 gather programs (conv3) -> conv64_wgrad_gather_kernel; anything else (wider images, operands
-  // rebuilt from (dA, y)) -> the chunk-at-a-time conv64_wgrad_kernel.
-  if (single_src && gf.y == nullptr && P.s2 && 32 + P.span + 32 <= RING_ROWS_S2) {
-    // 32-position chunks carrying all four destination classes (conv64_wgrad_ring_s2_kernel)
-    const int nch = (P.total_q + 31) / 32;
+  int launched_grid = grid, cpw = 0, wpg = 0;
+  // the ring kernels: contiguous chunk ranges per workgroup (ring re-use of the source rows), group by group
+  auto split = [&](int nch) {
     const int gpg = grid / P.G;
-    const int cpw = (nch + gpg - 1) / gpg;
-    const int wpg = (nch + cpw - 1) / cpw;
+    cpw = (nch + gpg - 1) / gpg;
+    wpg = (nch + cpw - 1) / cpw;
     launched_grid = wpg * P.G;
-    const size_t lds = (size_t)(RING_S2 + 4 * 32) * 256;
-    SRLZ_MAX_LDS(conv64_wgrad_ring_s2_kernel, lds);
-    SRLZ_LAUNCH(conv64_wgrad_ring_s2_kernel, dim3(launched_grid), dim3(256), lds, st, x, dy, partial, P, nch, cpw, wpg, x_bnp);
-  } else if (single_src && gf.y == nullptr && !P.s2 && tk + P.span + tk <= RING_ROWS && tk == 64 &&
-             (long long)P.N * P.Hs * P.Ws * 64 < (1LL << 32) && (long long)P.N * P.Hd * P.Wd * 64 < (1LL << 32) &&
-             (long long)P.total_q + 2 * P.PHW < (1LL << 31)) {  // (the row tables of the stride-1 kernel: 32-bit offsets)
-    // contiguous chunk ranges per workgroup (ring re-use of the source rows), group by group
-    const int gpg = grid / P.G;
-    const int cpw = (nchunks + gpg - 1) / gpg;
-    const int wpg = (nchunks + cpw - 1) / cpw;
-    launched_grid = wpg * P.G;
-    const size_t lds = (size_t)(RING + 64) * 256 + 2 * 64 * 4;  // ring + gradient rows + the two row tables = 80 KB
-    SRLZ_MAX_LDS(conv64_wgrad_ring_kernel, lds);
-    SRLZ_LAUNCH(conv64_wgrad_ring_kernel, dim3(launched_grid), dim3(256), lds, st, x, dy, partial, P, nchunks, cpw, wpg, x_bnp);
-  } else if (wgrad_gather_ok(P) && x_bnp == nullptr && gf.y == nullptr && tk == WG_TK) {
-    // stride-2 gather programs (conv3): the software-pipelined kernel; same grid, same partials as conv64_wgrad_kernel<true, 64>
-    const size_t lds = (size_t)(WG_TK + P.span + WG_TK) * 256 + (WG_SWORDS + WG_GWORDS) * 4;
-    SRLZ_MAX_LDS(conv64_wgrad_gather_kernel, lds);
-    SRLZ_LAUNCH(conv64_wgrad_gather_kernel, dim3(grid), dim3(256), lds, st, x, dy, partial, P, nchunks * P.G);
-  } else {
-    const size_t lds = wgrad_lds_bytes(P, tk);
-    SRLZ_REQUIRE(lds <= 160 * 1024, SRLZ_ERR_BAD_DESC, "conv64 wgrad: chunk needs %zu bytes of LDS", lds);
-#define SRLZ_WGRAD_LAUNCH(S2V, TKV)                                                                                        \
-  do {                                                                                                                     \
-    SRLZ_MAX_LDS((conv64_wgrad_kernel<S2V, TKV>), lds);                                                                     \
-    SRLZ_LAUNCH((conv64_wgrad_kernel<S2V, TKV>), dim3(grid), dim3(256), lds, st, x, dy, partial, P, nchunks * P.G, xf, gf);        \
-  } while (0)
-    if (P.s2) SRLZ_WGRAD_LAUNCH(true, 64);
-    else SRLZ_WGRAD_LAUNCH(false, 64);
-#undef SRLZ_WGRAD_LAUNCH
+  };
+  switch (wgrad_route(P, x_bnp, gf.y)) {
+    case WgradRoute::ring_s2: {
+      const int nch = (P.total_q + 31) / 32;
+      split(nch);
+      const size_t lds = (size_t)(RING_S2 + 4 * 32) * 256;
+      SRLZ_MAX_LDS(conv64_wgrad_ring_s2_kernel, lds);
+      SRLZ_LAUNCH(conv64_wgrad_ring_s2_kernel, dim3(launched_grid), dim3(256), lds, st, x, dy, partial, P, nch, cpw, wpg, x_bnp);
+      break;
+    }
+    case WgradRoute::ring: {
+      split(nchunks);
+      const size_t lds = (size_t)(RING + 64) * 256 + 2 * 64 * 4;  // ring + gradient rows + the two row tables = 80 KB
+      SRLZ_MAX_LDS(conv64_wgrad_ring_kernel, lds);
+      SRLZ_LAUNCH(conv64_wgrad_ring_kernel, dim3(launched_grid), dim3(256), lds, st, x, dy, partial, P, nchunks, cpw, wpg, x_bnp);
+      break;
+    }
+    case WgradRoute::gather: {
+      const size_t lds = wgrad_lds_bytes(P) + (WG_SWORDS + WG_GWORDS) * 4;
+      SRLZ_MAX_LDS(conv64_wgrad_gather_kernel, lds);
+      SRLZ_LAUNCH(conv64_wgrad_gather_kernel, dim3(grid), dim3(256), lds, st, x, dy, partial, P, nchunks * P.G);
+      break;
+    }
+    case WgradRoute::chunk: {
+      const size_t lds = wgrad_lds_bytes(P);
+      SRLZ_REQUIRE(lds <= 160 * 1024, SRLZ_ERR_BAD_DESC, "conv64 wgrad: chunk needs %zu bytes of LDS", lds);
+      if (P.s2) {
+        SRLZ_MAX_LDS((conv64_wgrad_kernel<true, WG_TK>), lds);
+        SRLZ_LAUNCH((conv64_wgrad_kernel<true, WG_TK>), dim3(grid), dim3(256), lds, st, x, dy, partial, P, nchunks * P.G, xf, gf);
+      } else {
+        SRLZ_MAX_LDS((conv64_wgrad_kernel<false, WG_TK>), lds);
+        SRLZ_LAUNCH((conv64_wgrad_kernel<false, WG_TK>), dim3(grid), dim3(256), lds, st, x, dy, partial, P, nchunks * P.G, xf, gf);
+      }
+      break;
+    }
   }
-  SRLZ_LAUNCH(conv64_wgrad_reduce, dim3((NTAPS * 4096 + 64 + 255) / 256), dim3(1024), 0, st, partial, launched_grid, dw_ref, dbias,
+  SRLZ_LAUNCH(conv64_wgrad_reduce, dim3((WGRAD_PARTIAL_FLOATS + 255) / 256), dim3(1024), 0, st, partial, launched_grid, dw_ref, dbias,
               d->transposed, 0);
   return 0;
 }
@@ -2931,59 +2900,43 @@ static int fused_bwd_grid(const ConvProg& P) {
   return g;
 }
 
-static bool fused_bwd_ok(const ConvProg& P) {
-  bool grouped = P.s2 && P.ss == 2 && P.G <= 2 && P.min_off == 0 && !P.dbg;
-  for (int t = 0; t < NTAPS; ++t) grouped = grouped && P.tsrc[t] == P.tsrc[t < 4 ? 0 : t < 6 ? 4 : t < 8 ? 6 : 8] && P.tdst[t] == 0;
-  const bool fits32 = P.src_gstride * 4 < (1LL << 32) - 65536 && P.dst_gstride * 4 < (1LL << 32) - 65536;
-  // the second and fourth class are requested and landed for the rows their taps can reach only (FB_NJ1 / FB_NJ3); they share the
-  // short LDS buffer As1 (TM + FB_REACH1 rows)
-  const bool reach = P.toff[4] >= 0 && P.toff[5] >= 0 && P.toff[4] < FB_REACH1 && P.toff[5] < FB_REACH1 && P.toff[8] >= 0 &&
-                     P.toff[8] <= FB_REACH3;
-  return grouped && fits32 && reach && TM + P.span <= GP_RP * GP_BATCH && GP_RP <= P.PHW && P.G * P.tpg >= 8;
-}
-
 extern "C" int srlz_conv64_gather_pipe_supported(const srlz_conv64_desc* d, int backward_data) {
-  if (check_desc(d)) return 0;
   ConvProg P;
-  if (program_for(&P, d, backward_data)) return 0;
+  if (with_program(d, backward_data, &P)) return 0;
   return gather_pipe_ok(P) ? 1 : 0;
 }
 
 extern "C" int srlz_conv64_bwd_fused_supported(const srlz_conv64_desc* d) {
-  if (check_desc(d) || !d->transposed || d->stride != 2) return 0;
   ConvProg P;
-  if (program_for(&P, d, 1)) return 0;
+  if (with_program(d, 1, &P) || !d->transposed || d->stride != 2) return 0;
   return fused_bwd_ok(P) ? 1 : 0;
 }
 
 extern "C" int srlz_conv64_bwd_fused_bn_rows(const srlz_conv64_desc* d) {
-  if (check_desc(d)) return -1;
   ConvProg P;
-  if (program_for(&P, d, 1)) return -1;
+  if (with_program(d, 1, &P)) return -1;
   return P.G * (4 * P.tpg + BNZ_BLOCKS);
 }
 
 extern "C" size_t srlz_conv64_bwd_fused_workspace(const srlz_conv64_desc* d) {
-  if (check_desc(d)) return 0;
   ConvProg P;
-  if (program_for(&P, d, 1)) return 0;
-  return (size_t)fused_bwd_grid(P) * (NTAPS * 4096 + 64) * sizeof(float);
+  if (with_program(d, 1, &P)) return 0;
+  return (size_t)fused_bwd_grid(P) * WGRAD_PARTIAL_FLOATS * sizeof(float);
 }
 
 extern "C" int srlz_conv64_bwd_fused(const float* x, const float* x_bnp, const float* dy, const srlz_bn_bwd_operand* dy_bn,
                                      const float* wpack_bwd, float* dx, float* dw_ref, float* dbias, float* x_bn_bwd_partial,
                                      void* ws, size_t ws_bytes, const srlz_conv64_desc* d, srlz_stream_t stream) {
-  if (int rc = check_desc(d)) return rc;
+  ConvProg P;
+  if (int rc = with_program(d, 1, &P)) return rc;
   SRLZ_REQUIRE(d->transposed && d->stride == 2, SRLZ_ERR_BAD_DESC, "conv64_bwd_fused: ConvTranspose2d(64, 64, 3, stride 2) only");
   SRLZ_REQUIRE(x && x_bnp && dy && dy_bn && wpack_bwd && dx && dw_ref && ws, SRLZ_ERR_NULL, "conv64_bwd_fused: null pointer");
   OpFuse gf;
   if (int rc = make_bwd_fuse(&gf, dy_bn, "conv64_bwd_fused")) return rc;
   SRLZ_REQUIRE(gf.dy_out == nullptr, SRLZ_ERR_BAD_DESC, "conv64_bwd_fused: d(loss)/dy is not materialised by this entry point");
-  ConvProg P;
-  if (int rc = program_for(&P, d, 1)) return rc;
   SRLZ_REQUIRE(fused_bwd_ok(P), SRLZ_ERR_BAD_DESC, "conv64_bwd_fused: shape not supported (ask srlz_conv64_bwd_fused_supported)");
   const int grid = fused_bwd_grid(P);
-  SRLZ_REQUIRE(ws_bytes >= (size_t)grid * (NTAPS * 4096 + 64) * sizeof(float), SRLZ_ERR_WORKSPACE,
+  SRLZ_REQUIRE(ws_bytes >= (size_t)grid * WGRAD_PARTIAL_FLOATS * sizeof(float), SRLZ_ERR_WORKSPACE,
                "conv64_bwd_fused: workspace too small (%zu bytes)", ws_bytes);
   hipStream_t st = as_stream(stream);
   // class rows (TM + span; TM + 32 for the short-reach classes), the a-tile, two weight slabs, rowinfo, records, row tables
@@ -2996,8 +2949,8 @@ extern "C" int srlz_conv64_bwd_fused(const float* x, const float* x_bnp, const f
   SRLZ_MAX_LDS(conv64_bwd_fused_kernel, lds);
   SRLZ_LAUNCH(conv64_bwd_fused_kernel, dim3(grid), dim3(GP_THREADS), lds, st, dy, wpack_bwd, dx, P, P.G * P.tpg, gf, fb);
   // second stage: fixed-order fp64 sum over the workgroups (the partial's bias block sits behind EACH workgroup's taps here)
-  SRLZ_LAUNCH(conv64_wgrad_reduce, dim3((NTAPS * 4096 + 64 + 255) / 256), dim3(1024), 0, st, (const float*)ws, grid, dw_ref, dbias, 1,
-              NTAPS * 4096 + 64);
+  SRLZ_LAUNCH(conv64_wgrad_reduce, dim3((WGRAD_PARTIAL_FLOATS + 255) / 256), dim3(1024), 0, st, (const float*)ws, grid, dw_ref, dbias, 1,
+              WGRAD_PARTIAL_FLOATS);
   if (x_bn_bwd_partial) {  // the records of the channels the fused kernel cannot sum from the activation (normally: zeros)
     SRLZ_LAUNCH(conv64_bnpart_zero_scale_kernel, dim3(BNZ_BLOCKS, P.G), dim3(256), 0, st, x, x_bnp, (const float*)dx, x_bn_bwd_partial,
                 (long long)P.N * P.Hd * P.Wd, fb.bn_rows, 4 * P.tpg);
@@ -3008,9 +2961,8 @@ extern "C" int srlz_conv64_bwd_fused(const float* x, const float* x_bnp, const f
 // Debug/test hook (host only, no GPU needed): dump the grid program so tests can interpret it on the CPU.
 // out[0..]: N,PH,PW,ss,Hs,Ws,ds,Hd,Wd,min_off,span,s2, then 9 x {src,dst,off,w}.  Returns number of ints or <0.
 extern "C" int srlz_conv64_debug_program(const srlz_conv64_desc* d, int backward_data, int* out, int cap) {
-  if (int rc = check_desc(d)) return rc;
   ConvProg P;
-  if (int rc = program_for(&P, d, backward_data)) return rc;
+  if (int rc = with_program(d, backward_data, &P)) return rc;
   if (cap < 12 + 4 * NTAPS) return SRLZ_ERR_WORKSPACE;
   int i = 0;
   out[i++] = P.N; out[i++] = P.PH; out[i++] = P.PW; out[i++] = P.ss; out[i++] = P.Hs; out[i++] = P.Ws;

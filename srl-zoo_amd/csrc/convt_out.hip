@@ -27,13 +27,13 @@ namespace {
 
 __device__ __forceinline__ int xcd_wg(int b, int nb) { return xcd_remap(b, nb); }
 
-// Branch-free conditional stores (as conv64.hip's gp_buffer): a buffer resource over one image; a lane that must not write passes
+// Branch-free conditional stores (common.h: raw_buffer): a buffer resource over one image; a lane that must not write passes
 // OS_DROP and the hardware drops its store.  A store inside a branch makes hipcc's wait insertion give up at the next loop header
 // (everything is waited for: vmcnt is in-order and the path through the branch has an unknown number of stores in flight) — which
 // would empty the rows-in-flight queue of these kernels once per trip.  A NULL tensor becomes a zero-sized resource: all dropped.
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t os_buffer(float* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(p, 0, (int)(p ? bytes : 0u), 0x00020000);
+  return raw_buffer(p, p ? bytes : 0u);
 }
 constexpr unsigned OS_DROP = 0xFFFFFF00u;
 __device__ __forceinline__ void os_store2(__amdgpu_buffer_rsrc_t r, unsigned byte_off, float a, float b) {

@@ -24,7 +24,7 @@
 //           from L2 into the MFMA's A operand, four components ahead; V as ds_read_b128 one component ahead (one read feeds four MFMAs);
 //   epilogue: 16 -> 4 fold in registers, bias, 16-byte NHWC stores (a lane holds 4 consecutive channels of one patch), BatchNorm partial
 //           sums (sum y, sum y^2) of the tile as one record; PSUM (conv2's data gradient = d pooled1): the pooled block's two
-//           BatchNorm-BACKWARD sums instead (WinoPoolSum).
+//           BatchNorm-BACKWARD sums instead (PoolSum).
 // Weight gradient — conv64_wino_wgrad_kernel: the transposed algorithm (below).
 // LDS layouts are conflict-free against the hardware's lane groups: ds_read_b128 is served as {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31},
 // ... (not 16 consecutive lanes), ds_write_b64 in runs of 16 lanes over 32 banks (MI355X_MICROARCH.md, LDS).
@@ -51,19 +51,6 @@ struct WinoProg {
   int sPPI, sPB;
   long long gstride; // floats of one group's tensor
 };
-
-void wn_fastdiv_init(unsigned d, unsigned* m, int* sh) {  // (conv64.hip: Granlund-Montgomery for 31-bit dividends, d >= 2)
-  int l = 0;
-  while ((1u << l) < d) ++l;
-  if (l == 0) l = 1;
-  *m = (unsigned)((((unsigned long long)1 << (31 + l)) / d) + 1);
-  *sh = l - 1;
-}
-__device__ __forceinline__ int wn_div(int q, unsigned m, int sh) { return (int)(__umulhi((unsigned)q, m) >> sh); }
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wn_buffer(const void* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // U = G g G^T per (co, ci), G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]], in the kernel's layout
@@ -117,9 +104,9 @@ struct WinoPatch {  // a thread's patch for the transform role: byte offsets of 
 __device__ __forceinline__ void wn_patch(WinoPatch& wp, const WinoProg& P, int tile_in_group, int t_pt, int t_cp, int* ptab_slot) {
   const int pl = tile_in_group * WN_TP + t_pt;
   const bool ok = pl < P.ppg;
-  const int n = wn_div(pl, P.mPPI, P.sPPI);
+  const int n = fastdiv(pl, P.mPPI, P.sPPI);
   const int rem = pl - n * P.ppi;
-  const int a = wn_div(rem, P.mPB, P.sPB);
+  const int a = fastdiv(rem, P.mPB, P.sPB);
   const int b = rem - a * P.PB;
   const int pix = (n * P.H + 2 * a) * P.W + 2 * b;
   const unsigned vbase = (unsigned)pix * 256u + (unsigned)t_cp * 8u;
@@ -251,20 +238,6 @@ __device__ __forceinline__ void wn_mfma_phase(f32x4 (&acc)[16][2], f32x4 (&aq)[W
   __builtin_amdgcn_sched_barrier(0);
 }
 
-// Epilogue option of the data-gradient launch whose output is the gradient of a POOLED map (conv2's data gradient = d pooled1; cf.
-// conv64.hip's PoolSum / conv64_dgrad_poolsum_kernel): instead of BatchNorm-forward statistics the tile's record receives the two
-// BatchNorm-BACKWARD sums of the block that produced the pooled map,  sum dz  and  sum dz * xhat  with dz = d pooled where pooled > 0
-// (the gradient of max-pool + ReLU lives at the window's argmax, where the pooled value IS relu(bn(y)): xhat follows from it).
-// y / argmax are only touched for channels whose BatchNorm scale is (almost) 0.
-struct WinoPoolSum {
-  const float* pooled;    // [N,H,W,64] like the launch's output; NULL = off
-  const float* bnp;       // records of the pooled block's BatchNorm (256 floats per group)
-  const float* y;         // raw convolution output under the pooling [N,YH,YW,64]
-  const uint8_t* argmax;  // [N,H,W,64]
-  long long y_gstride;    // floats between two groups' images in y
-  int YH, YW, pad;
-};
-
 __device__ __forceinline__ float wn_row16_sum(float v) {  // sum over the 16 lanes of a row (every lane gets it): four rotating DPP adds
   v += __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(v), 0x128, 0xf, 0xf, false));
   v += __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(v), 0x124, 0xf, 0xf, false));
@@ -279,7 +252,7 @@ __device__ __forceinline__ float wn_row16_sum(float v) {  // sum over the 16 lan
 // (which leaves 0 for them).  A group without such a channel (the normal case) costs one ~4 us launch that writes zero records; with one,
 // this is a pass over (d pooled, argmax) and a gather from y: rare, and slow on purpose.
 constexpr int WN_ZBLOCKS = 64;
-__global__ __launch_bounds__(256) void conv64_wino_poolsum_zero_scale_kernel(const float* __restrict__ dx, const WinoPoolSum ps, float* __restrict__ partial,
+__global__ __launch_bounds__(256) void conv64_wino_poolsum_zero_scale_kernel(const float* __restrict__ dx, const PoolSum ps, float* __restrict__ partial,
                                                                             int N, int H, int W, long long gstride, int rows, int first_row) {
   const int g = blockIdx.y;
   const float* __restrict__ rec = ps.bnp + g * 256;
@@ -302,7 +275,7 @@ __global__ __launch_bounds__(256) void conv64_wino_poolsum_zero_scale_kernel(con
         if ((zmask >> j) & 1u) {
           const int a = (packed >> (8 * j)) & 0xff;
           const int iy = yy * 2 - ps.pad + a / 3, ix = xx * 2 - ps.pad + a % 3;
-          const float vy = ps.y[g * ps.y_gstride + ((size_t)(n * ps.YH + iy) * ps.YW + ix) * 64 + c4 * 4 + j];
+          const float vy = ps.y[g * ps.y_gstride + ((size_t)(n * ps.H + iy) * ps.W + ix) * 64 + c4 * 4 + j];
           if (vy * psc[j] + psh[j] > 0.f) {
             s1[j] += (double)v[j];
             s2[j] += (double)(v[j] * ((vy - mean[j]) * pinv[j]));
@@ -317,7 +290,7 @@ template <bool PSUM, bool FUSE>
 __global__ __launch_bounds__(WN_THREADS, 2) void conv64_wino_kernel(const float* __restrict__ x_all, const float* __restrict__ upack,
                                                                     const float* __restrict__ bias, float* __restrict__ y_all,
                                                                     float* __restrict__ stats_partial, const WinoProg P, int ntiles,
-                                                                    const WinoPoolSum ps, const float* __restrict__ x_bnp) {
+                                                                    const PoolSum ps, const float* __restrict__ x_bnp) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* Vs = (float*)smem;                // [2 (chunk parity)][WN_VCHUNK]
   int* ptab = (int*)(Vs + 2 * WN_VCHUNK);  // [2 (tile parity)][32]: pixel index of output (2a, 2b) of a tile's patches, -1 = no such patch
@@ -337,7 +310,7 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv64_wino_kernel(const float*
   float* Vw = Vs + (t_pt * 4 + ((t_cp >> 1) ^ (((t_pt >> 2) & 1) << 1))) * 4 + 2 * (t_cp & 1);
   const float* Bp = Vs + (l15 * 4 + (g ^ (((l15 >> 2) & 1) << 1))) * 4;
   const unsigned uvoff = (unsigned)(g * 64 + 16 * cb + l15) * 16u;
-  const __amdgpu_buffer_rsrc_t ub = wn_buffer(upack, 4u * WN_CHUNK * 4u);
+  const __amdgpu_buffer_rsrc_t ub = raw_buffer(upack, 4u * WN_CHUNK * 4u);
 
   // XCD-contiguous runs of tiles (block b runs on XCD b % 8: neighbouring tiles share input rows in that XCD's L2)
   const int xcd = blockIdx.x & 7, wi = blockIdx.x >> 3, wpx = gridDim.x >> 3;
@@ -349,7 +322,7 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv64_wino_kernel(const float*
 
   const unsigned xbytes = (unsigned)(P.gstride * 4) + (unsigned)(P.W + 1) * 256u;
   const unsigned ybytes = (unsigned)(P.gstride * 4);
-  const __amdgpu_buffer_rsrc_t sbuf = wn_buffer(stats_partial, stats_partial ? (unsigned)(P.G * (P.tpg + (PSUM ? WN_ZBLOCKS : 0))) * 512u : 0u);
+  const __amdgpu_buffer_rsrc_t sbuf = raw_buffer(stats_partial, stats_partial ? (unsigned)(P.G * (P.tpg + (PSUM ? WN_ZBLOCKS : 0))) * 512u : 0u);
 
   // Pipeline (one barrier per chunk): during the matrix work of chunk c (from V[c & 1]) chunk c + 1 is transformed into V[(c + 1) & 1]
   // — at the top of the phase, from the registers its raw patch was loaded into during chunk c - 1 — and chunk c + 2 is requested.
@@ -360,7 +333,7 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv64_wino_kernel(const float*
   {
     const int tile = tbase + k;
     const int grp = tile / P.tpg;
-    const __amdgpu_buffer_rsrc_t xb = wn_buffer(x_all + grp * P.gstride - (P.W + 1) * 64, xbytes);
+    const __amdgpu_buffer_rsrc_t xb = raw_buffer(x_all + grp * P.gstride - (P.W + 1) * 64, xbytes);
     wn_patch(wp, P, tile - grp * P.tpg, t_pt, t_cp, ptab + t_pt);
     const float* bnrec = FUSE ? x_bnp + grp * 256 : nullptr;
     wn_request<FUSE>(rw, wp, xb, P.W, 0, bnrec, t_cp);
@@ -373,12 +346,12 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv64_wino_kernel(const float*
     const int tile = tbase + k;
     const int grp = tile / P.tpg;
     const int til = tile - grp * P.tpg;
-    const __amdgpu_buffer_rsrc_t xb = wn_buffer(x_all + grp * P.gstride - (P.W + 1) * 64, xbytes);
+    const __amdgpu_buffer_rsrc_t xb = raw_buffer(x_all + grp * P.gstride - (P.W + 1) * 64, xbytes);
     const int k2 = k + wpx;
     const bool more = k2 < tcnt;
     const int tile2 = tbase + (more ? k2 : k);  // (past the last tile: the same tile once more — chunks nobody multiplies)
     const int grp2 = tile2 / P.tpg;
-    const __amdgpu_buffer_rsrc_t xb2 = wn_buffer(x_all + grp2 * P.gstride - (P.W + 1) * 64, xbytes);
+    const __amdgpu_buffer_rsrc_t xb2 = raw_buffer(x_all + grp2 * P.gstride - (P.W + 1) * 64, xbytes);
     int uo = 0;  // (the weights are the same for every tile: without the opaque offset hipcc hoists their loads out of the tile loop)
     asm volatile("" : "+s"(uo));
     f32x4 acc[16][2];
@@ -400,7 +373,7 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv64_wino_kernel(const float*
     }
     // ---- epilogue: Y = A^T M A per patch, bias, stores, BatchNorm partial sums.  A lane holds, of the patches 32 pb + 16 s + l15,
     // the channels 16 cb + 4 g + {0..3}
-    const __amdgpu_buffer_rsrc_t yb = wn_buffer(y_all + grp * P.gstride, ybytes);
+    const __amdgpu_buffer_rsrc_t yb = raw_buffer(y_all + grp * P.gstride, ybytes);
     f32x4 s4 = {0.f, 0.f, 0.f, 0.f}, q4 = {0.f, 0.f, 0.f, 0.f};
     f32x4 bias4 = {0.f, 0.f, 0.f, 0.f};
     if (bias) bias4 = *(const f32x4*)(bias + 16 * cb + 4 * g);
@@ -409,7 +382,7 @@ __global__ __launch_bounds__(WN_THREADS, 2) void conv64_wino_kernel(const float*
     // and sum dz * xhat = pA q4 + pB s4 at the end.  A channel whose scale is (almost) 0 contributes nothing here (threshold +inf,
     // pA = pB = 0) and is summed by the cold loop below from the convolution output under the recorded argmax.
     f32x4 pA = {0.f, 0.f, 0.f, 0.f}, pB = pA, pthr = pA;
-    const __amdgpu_buffer_rsrc_t zb = wn_buffer(PSUM ? ps.pooled + grp * P.gstride : nullptr, PSUM ? ybytes : 0u);
+    const __amdgpu_buffer_rsrc_t zb = raw_buffer(PSUM ? ps.pooled + grp * P.gstride : nullptr, PSUM ? ybytes : 0u);
     if constexpr (PSUM) {
       const float* __restrict__ rec = ps.bnp + grp * 256 + 16 * cb + 4 * g;
       const f32x4 mean = *(const f32x4*)rec, pinv = *(const f32x4*)(rec + 64), psc = *(const f32x4*)(rec + 128), psh = *(const f32x4*)(rec + 192);
@@ -487,8 +460,8 @@ int wino_program(WinoProg* P, const srlz_conv64_desc* d) {
   if (gfl * 4 + (long long)(P->W + 1) * 256 >= 0x7FFF0000LL || ppg + WN_TP >= (1LL << 31) || ppi < 2) return 1;
   P->ppi = (int)ppi; P->ppg = (int)ppg; P->tpg = (int)((ppg + WN_TP - 1) / WN_TP);
   P->gstride = gfl;
-  wn_fastdiv_init((unsigned)P->ppi, &P->mPPI, &P->sPPI);
-  wn_fastdiv_init((unsigned)P->PB, &P->mPB, &P->sPB);
+  fastdiv_init((unsigned)P->ppi, &P->mPPI, &P->sPPI);
+  fastdiv_init((unsigned)P->PB, &P->mPB, &P->sPB);
   return 0;
 }
 
@@ -527,9 +500,9 @@ struct WinoWgradPatch { unsigned vtop, vmid, vbot, vdy; bool lef, rig; };
 
 __device__ __forceinline__ void wg_patch(WinoWgradPatch& wp, const WinoWgradProg& P, int patch, int chan_pair) {
   const bool ok = patch < P.total;
-  const int n = wn_div(patch, P.mPPI, P.sPPI);
+  const int n = fastdiv(patch, P.mPPI, P.sPPI);
   const int rem = patch - n * P.ppi;
-  const int a = wn_div(rem, P.mPB, P.sPB);
+  const int a = fastdiv(rem, P.mPB, P.sPB);
   const int b = rem - a * P.PB;
   const int pix = (n * P.H + 2 * a) * P.W + 2 * b;
   const unsigned vbase = (unsigned)pix * 256u + (unsigned)chan_pair * 8u;
@@ -660,8 +633,8 @@ __device__ __forceinline__ void wg_body(const float* __restrict__ x, const float
   const int tz = cq * 4 * WG_COMP + (h * 64 + 32 * ch + l31) * 2, tv = cq * 4 * WG_COMP + (h * 64 + l31) * 2;
 
   const long long tfl = (long long)P.N * P.H * P.W * 64;
-  const __amdgpu_buffer_rsrc_t xb = wn_buffer(x - (P.W + 1) * 64, (unsigned)(tfl * 4) + (unsigned)(P.W + 1) * 256u);
-  const __amdgpu_buffer_rsrc_t gb = wn_buffer(dy, (unsigned)(tfl * 4));
+  const __amdgpu_buffer_rsrc_t xb = raw_buffer(x - (P.W + 1) * 64, (unsigned)(tfl * 4) + (unsigned)(P.W + 1) * 256u);
+  const __amdgpu_buffer_rsrc_t gb = raw_buffer(dy, (unsigned)(tfl * 4));
 
   f32x16 acc[4][2];
 #pragma unroll
@@ -801,13 +774,13 @@ extern "C" int srlz_conv64_wino_tiles(const srlz_conv64_desc* d) {
 }
 
 static int wino_launch(const float* x, const float* upack, const float* bias, float* y, float* partial, const WinoProg& P,
-                       const WinoPoolSum* ps, const float* x_bnp, srlz_stream_t stream) {
+                       const PoolSum* ps, const float* x_bnp, srlz_stream_t stream) {
   const int ntiles = P.G * P.tpg;
   int grid = 2 * srlz_device_cus();  // two workgroups per CU (64 KB of LDS, 256 registers each): one's barriers, landings and epilogue
   if (ntiles < grid) grid = ntiles;  // run under the other's matrix work
   grid = (grid + 7) & ~7;
   const size_t lds = (size_t)2 * WN_VCHUNK * 4 + 2 * WN_TP * 4;
-  const WinoPoolSum none = {nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
+  const PoolSum none = SRLZ_NO_POOLSUM;
   hipStream_t st = as_stream(stream);
   if (ps) {
     SRLZ_MAX_LDS((conv64_wino_kernel<true, false>), lds);
@@ -862,7 +835,7 @@ extern "C" int srlz_conv64_wino_bwd_data_pool_sums(const float* dy, const float*
   SRLZ_REQUIRE(pd->n == d->n && pd->hp == d->hi && pd->wp == d->wi && !pd->out_nchw && (pd->groups > 1 ? pd->groups : 1) == P.G,
                SRLZ_ERR_BAD_DESC, "conv64_wino_bwd_data_pool_sums: the pooled map [%d,%d,%d] is not this layer's input [%d,%d,%d]", pd->n, pd->hp,
                pd->wp, d->n, d->hi, d->wi);
-  const WinoPoolSum ps = {pooled, pool_bnp, pool_y, pool_argmax, (long long)(pd->n / P.G) * pd->h * pd->w * 64, pd->h, pd->w, pd->pool_pad};
+  const PoolSum ps = {pooled, pool_bnp, pool_y, pool_argmax, (long long)(pd->n / P.G) * pd->h * pd->w * 64, pd->h, pd->w, pd->pool_pad};
   return wino_launch(dy, upack_bwd, nullptr, dx, bn_bwd_partial, P, &ps, nullptr, stream);
 }
 
