@@ -1,5 +1,6 @@
 """The route table of the 64->64 convolution family, pinned: which virtual-grid program csrc/conv64.hip builds for a descriptor and
-which kernels take it (the host-only answers of the C ABI), against tests/golden/conv64_routes.json.  Host code only: no GPU.
+which kernels take it (the host-only answers of the C ABI; the route predicates sit next to their kernels, in csrc/conv64_pipe.hip and
+csrc/conv64_wgrad.hip), against tests/golden/conv64_routes.json.  Host code only: no GPU.
 
 The fixture was recorded with the library as it was BEFORE the route predicates were gathered in one place, so the test says that
 gathering them changed no decision.  To record it again (only when a route is meant to change):  python tests/test_conv64_routes_cpu.py

@@ -22,7 +22,7 @@ HOT = ("conv64_fwd_kernel<4, false>", "conv64_fwd_kernel<4, true>", "conv64_wgra
 
 
 @pytest.mark.skipif(not os.path.exists(isa_audit.HIPCC) and shutil.which("hipcc") is None, reason="needs hipcc")
-@pytest.mark.parametrize("source", ["conv64.hip", "skinny.hip", "convt_out.hip", "linear.hip"])
+@pytest.mark.parametrize("source", ["conv64.hip", "conv64_pipe.hip", "conv64_wgrad.hip", "convn.hip", "skinny.hip", "convt_out.hip", "linear.hip"])
 def test_no_serialised_stores_and_no_spills_in_hot_kernels(source):
     ks = list(isa_audit.kernels(isa_audit.disassemble(os.path.join(isa_audit.CSRC, source))))
     names = isa_audit.demangle([k for k, _ in ks])
@@ -37,6 +37,7 @@ def test_no_serialised_stores_and_no_spills_in_hot_kernels(source):
                 seen.add(hot)
                 assert a["scratch_reloads"] == 0, "%s spills (%d scratch reloads)" % (name, a["scratch_reloads"])
     if source != "linear.hip":
-        where = lambda h: "conv64.hip" if h.startswith("conv64") else "convt_out.hip" if h.startswith("convT_out_os") else "skinny.hip"
+        where = lambda h: ("conv64_wgrad.hip" if h.startswith("conv64_wgrad") else "conv64_pipe.hip" if h.startswith("conv64_gather_pipe") else
+                           "conv64.hip" if h.startswith("conv64") else "convt_out.hip" if h.startswith("convT_out_os") else "skinny.hip")
         expected = [h for h in HOT if where(h) == source]
         assert set(expected) <= seen, "kernels renamed? missing %s" % sorted(set(expected) - seen)

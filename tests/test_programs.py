@@ -117,7 +117,7 @@ def test_program_tap_grouping(cabi, hi, s, p, t):
         assert sorted(w for (_, _, _, w) in P["taps"]) == list(range(9))
 
 
-RING_ROWS, RING_MIRROR = 246, 8  # csrc/conv64.hip (the ring shrank from 248 rows when the two row tables moved into its 80 KB)
+RING_ROWS, RING_MIRROR = 246, 8  # csrc/conv64_wgrad.hip (the ring shrank from 248 rows when the two row tables moved into its 80 KB)
 
 
 @pytest.mark.parametrize("hi,s,p,t", [(56, 1, 1, 0), (6, 2, 0, 1), (13, 2, 0, 1), (27, 2, 0, 1), (55, 2, 0, 1), (9, 1, 1, 0)])
@@ -161,7 +161,7 @@ def test_wgrad_ring_schedule_never_aliases(cabi, hi, s, p, t):
 
 
 def _rowtab_entry(P, q):
-    """rowtab_build / gtab_build of csrc/conv64.hip for grid position q of one BatchNorm group: pixel index of the row's class-(0,0)
+    """rowtab_build (csrc/conv64_tile.h) / gtab_build (csrc/conv64_pipe.hip) for grid position q of one BatchNorm group: pixel index of the row's class-(0,0)
     source pixel << 4 | bit k: source class k = (cy << 1) | cx lies inside the image; 0 = no image."""
     PHW = P["PH"] * P["PW"]
     n1 = (q + PHW) // PHW  # (shifted by one image, as the kernel does for the negative q of the first tile)
