@@ -4,7 +4,6 @@
 order, initialisation and state_dict keys are the reference's, models/models.py:47-83), but they are never *called*:
 the forward below reads their parameters and runs the MI355X kernels.
 """
-import os
 import torch
 
 from . import ops
@@ -167,16 +166,12 @@ def _record_activation(idx, y, st, bn, training):
 # Frozen ResNet-18 trunk of EmbeddingNet (reference models/triplet.py:16 -> torchvision resnet18), FORWARD ONLY.
 # ---------------------------------------------------------------------------------------------------------------------
 def _packed(conv, d):
-    """The kernel-layout copy of a frozen convolution's weights, kept on the module and rebuilt only if the parameter was
-    moved or written (load_state_dict, .to(device))."""
-    key = (conv.weight.data_ptr(), conv.weight._version)
-    cached = getattr(conv, "_srlz_pack", None)
-    if cached is None or cached[0] != key:
+    """The kernel-layout copy of a frozen convolution's weights for srlz_convn_fwd, one per module (ops._cached_pack)."""
+    def build():
         pk = torch.empty(ops.C.convn_packed_floats(d), dtype=torch.float32, device=conv.weight.device)
         ops.C.convn_pack_weights(ops.ptr(conv.weight), ops.ptr(pk), d, ops.stream())
-        cached = (key, pk)
-        conv._srlz_pack = cached
-    return cached[1]
+        return pk
+    return ops._cached_pack(conv, "_srlz_pack", build)
 
 
 def _bn_record(bn, stats, tiles, count, training, device, groups=1):
@@ -200,58 +195,24 @@ def _bn_record(bn, stats, tiles, count, training, device, groups=1):
     return bnp
 
 
-def _packed64(conv, d):
-    """As _packed, for a 64 -> 64 3x3 convolution in the conv64 kernels' layout (the forward pack only is used)."""
-    key = (conv.weight.data_ptr(), conv.weight._version)
-    cached = getattr(conv, "_srlz_pack64", None)
-    if cached is None or cached[0] != key:
-        pk = torch.empty((2, ops.C.conv64_packed_floats()), dtype=torch.float32, device=conv.weight.device)
-        ops.C.conv64_pack_weights(ops.ptr(conv.weight), ops.ptr(pk[0]), ops.ptr(pk[1]), d, ops.stream())
-        cached = (key, pk)
-        conv._srlz_pack64 = cached
-    return cached[1]
-
-
-def _packed_wino(conv):
-    """As _packed, for a 64 -> 64 3x3 stride-1 convolution in the Winograd kernel's layout (G g G^T, forward direction)."""
-    key = (conv.weight.data_ptr(), conv.weight._version)
-    cached = getattr(conv, "_srlz_pack_wino", None)
-    if cached is None or cached[0] != key:
-        pk = torch.empty(ops.C.conv64_wino_packed_floats(), dtype=torch.float32, device=conv.weight.device)
-        ops.C.conv64_wino_pack_weights(ops.ptr(conv.weight), ops.ptr(pk), None, ops.stream())
-        cached = (key, pk)
-        conv._srlz_pack_wino = cached
-    return cached[1]
-
-
 def _convn(x, conv, bn, training, x_bnp=None, groups=1):
     """raw = conv(x or relu(bn_prev(x))) for an NHWC tensor + the BatchNorm record(s) of `bn` over that output; `groups` independent
     calls batched along n (x_bnp and the returned records are [groups][channel blocks][256])."""
     n, hi, wi, cin = x.shape
     k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-    ho, wo = (hi + 2 * p - k) // s + 1, (wi + 2 * p - k) // s + 1
     if cin == 64 and conv.out_channels == 64 and k == 3 and s == 1 and p == 1:
-        # layer1 of the trunk (four 64 -> 64 3x3 convolutions at 56 x 56): the auto-encoder's own conv2 kernel — row tables, 16-byte
-        # epilogue stores, fused relu(bn(.)) operand — instead of the general-channel-count kernel (0.73 against 0.56 of the matrix peak)
+        # layer1 of the trunk (four 64 -> 64 3x3 convolutions at 56 x 56): the auto-encoder's own conv2 kernels — Winograd F(2x2, 3x3)
+        # on even maps, else row tables, 16-byte epilogue stores; the raw output of a block's first convolution goes in through the fused
+        # relu(bn(.)) operand (x_bnp) — instead of the general-channel-count kernel (0.73 against 0.56 of the matrix peak)
         d = ops.conv64_desc(n, hi, wi, 1, 1, False, groups)
-        y = torch.empty((n, ho, wo, 64), dtype=torch.float32, device=x.device)
-        if ops.C.conv64_wino_supported(d):
-            # ... as Winograd F(2x2, 3x3) (csrc/wino.hip) on even maps: a materialised input (the first convolution of a block) as it is, the
-            # raw output of the block's first convolution through the fused relu(bn(.)) landing (x_bnp)
-            tiles = ops.C.conv64_wino_tiles(d)
-            stats = torch.empty((1, tiles, 128), dtype=torch.float32, device=x.device) if training else None
-            ops.C.conv64_wino_fwd(ops.ptr(x), ops.ptr(_packed_wino(conv)), None, ops.ptr(y), ops.ptr(stats), ops.ptr(x_bnp), d, ops.stream())
-            return y, _bn_record(bn, stats, tiles, n // groups * ho * wo, training, x.device, groups)
-        tiles = ops.C.conv64_fwd_tiles(d)
-        stats = torch.empty((1, tiles, 128), dtype=torch.float32, device=x.device) if training else None
-        ops.C.conv64_fwd(ops.ptr(x), ops.ptr(_packed64(conv, d)[0]), None, ops.ptr(y), ops.ptr(stats), ops.ptr(x_bnp), d, ops.stream())
-        return y, _bn_record(bn, stats, tiles, n // groups * ho * wo, training, x.device, groups)
-    d = ops.ConvNDesc(n, hi, wi, ho, wo, cin, conv.out_channels, k, s, p, groups)
-    y = torch.empty((n, ho, wo, conv.out_channels), dtype=torch.float32, device=x.device)
-    tiles = ops.C.convn_fwd_tiles(d)
-    stats = torch.empty((conv.out_channels // 64, tiles, 128), dtype=torch.float32, device=x.device) if training else None
-    ops.C.convn_fwd(ops.ptr(x), ops.ptr(_packed(conv, d)), ops.ptr(y), ops.ptr(stats), ops.ptr(x_bnp), d, ops.stream())
-    return y, _bn_record(bn, stats, tiles, n // groups * ho * wo, training, x.device, groups)
+        y, stats, _, _ = ops._conv64_forward(x, conv.weight, None, d, training, x_bnp, frozen=conv)
+    else:
+        d = ops.ConvNDesc(n, hi, wi, (hi + 2 * p - k) // s + 1, (wi + 2 * p - k) // s + 1, cin, conv.out_channels, k, s, p, groups)
+        y = torch.empty((n, d.ho, d.wo, conv.out_channels), dtype=torch.float32, device=x.device)
+        stats = torch.empty((conv.out_channels // 64, ops.C.convn_fwd_tiles(d), 128), dtype=torch.float32, device=x.device) if training else None
+        ops.C.convn_fwd(ops.ptr(x), ops.ptr(_packed(conv, d)), ops.ptr(y), ops.ptr(stats), ops.ptr(x_bnp), d, ops.stream())
+    tiles = stats.shape[-2] if training else 0  # (per block of 64 output channels)
+    return y, _bn_record(bn, stats, tiles, n // groups * d.ho * d.wo, training, x.device, groups)
 
 
 def resnet18_forward(trunk, x, training, groups=1):
@@ -271,15 +232,11 @@ def resnet18_forward(trunk, x, training, groups=1):
         assert c == 3, "the ResNet-18 trunk takes one 3-channel view at a time"
         assert groups >= 1 and n % groups == 0, (n, groups)
         # stem: Conv2d(3,64,7,2,3) -> BatchNorm2d -> ReLU -> MaxPool2d(3,2,1): the kernels of the auto-encoder's first block
-        d = ops._skinny_desc(n, c, h, w, 0, groups)
-        y = torch.empty((n, d.hf, d.wf, 64), dtype=torch.float32, device=x.device)
-        tiles = ops.C.skinny_tiles(d)
-        stats = torch.empty((1, tiles, 128), dtype=torch.float32, device=x.device) if training else None
-        ops.C.conv1_fwd(ops.ptr(x), ops.ptr(trunk.conv1.weight), ops.ptr(y), ops.ptr(stats), d, ops.stream())
-        bnp = _bn_record(trunk.bn1, stats, tiles, n // groups * d.hf * d.wf, training, x.device, groups)
-        hp, wp = (d.hf + 2 - 3) // 2 + 1, (d.wf + 2 - 3) // 2 + 1
-        act = torch.empty((n, hp, wp, 64), dtype=torch.float32, device=x.device)
-        ops.C.bn_relu_pool_fwd(ops.ptr(y), ops.ptr(bnp), ops.ptr(act), None, ops.PoolDesc(n, d.hf, d.wf, hp, wp, 1, 0, groups), ops.stream())
+        _, _, y, stats, d = ops._conv1_forward(x, trunk.conv1.weight, groups, training)
+        bnp = _bn_record(trunk.bn1, stats, stats.shape[0] if training else 0, n // groups * d.hf * d.wf, training, x.device, groups)
+        pd = ops.pool_desc(n, d.hf, d.wf, 1, False, groups)
+        act = torch.empty((n, pd.hp, pd.wp, 64), dtype=torch.float32, device=x.device)
+        ops.C.bn_relu_pool_fwd(ops.ptr(y), ops.ptr(bnp), ops.ptr(act), None, pd, ops.stream())
         for layer in (trunk.layer1, trunk.layer2, trunk.layer3, trunk.layer4):
             for block in layer:
                 c1, rec1 = _convn(act, block.conv1, block.bn1, training, groups=groups)

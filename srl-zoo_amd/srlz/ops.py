@@ -5,6 +5,7 @@ The reference relies on ``loss.backward()`` (models/learner.py:489); here each f
 used for storage only: no torch compute op touches an activation.  Activations are NHWC between the first conv and the
 last transposed conv; images and everything the caller sees stay in the reference's NCHW layout.
 """
+import ctypes
 import weakref
 
 import torch
@@ -43,7 +44,6 @@ class batch_groups(object):
 def cur_groups(training):
     return _GROUPS if training else 1
 
-_workspaces = {}
 
 # ---- optional per-launch timing (bench.py's roofline leg): HIP events recorded on the stream the kernels run on ----
 _timers_on = False
@@ -135,6 +135,9 @@ def _conv64_key(d, what):
     return "%s s%d n%d %dx%d->%dx%d %s" % ("convT" if d.transposed else "conv", d.stride, d.n, d.hi, d.wi, d.ho, d.wo, what)
 
 
+_workspaces = {}
+
+
 def _ws(nbytes, device, slot=0):
     """Grow-only scratch buffer per (device, current stream, slot): work on one stream is ordered, so a buffer is only
     ever shared by launches of the stream that owns it."""
@@ -146,7 +149,13 @@ def _ws(nbytes, device, slot=0):
     return buf
 
 
-import os as _os
+def _stats_output(ctx, stats, device):
+    """The per-tile statistics of a convolution as the non-differentiable second output of its node (empty when none were asked for)."""
+    if stats is None:
+        stats = torch.empty(0, device=device)
+    ctx.mark_non_differentiable(stats)
+    ctx.set_materialize_grads(False)  # no zero tensor for the statistics output in backward
+    return stats
 
 
 def _check(t, name):
@@ -224,22 +233,33 @@ def _skinny_desc(n, c, himg, wimg, kind, groups=1):
     return SkinnyDesc(n, c, himg, wimg, hf, wf, kind, groups)
 
 
+def _conv1_forward(x, w, groups, want_stats):
+    """conv1 over float images or the loader's bytes (normalised inside the kernel's window staging) -> the checked (x, w), y (NHWC),
+    the per-tile statistics of y (or None) and the descriptor."""
+    u8 = is_u8_frames(x)
+    x, w = (_check_u8(x, "conv1 input") if u8 else _check(x, "conv1 input")), _check(w, "conv1 weight")
+    n, c, h, wd = x.shape
+    d = _skinny_desc(n, c, h, wd, 0, groups)
+    y = torch.empty((n, d.hf, d.wf, 64), dtype=torch.float32, device=x.device)
+    stats = torch.empty((C.skinny_tiles(d), 128), dtype=torch.float32, device=x.device) if want_stats else None
+    if u8:
+        lut = norm_lut(x.device)
+        _launch("skinny_conv_kernel", _skinny_key(d, "fwd u8"), _conv1_flop(d),
+                lambda: C.conv1_fwd_u8(ptr(x), ptr(lut), ptr(w), ptr(y), ptr(stats), d, stream()))
+    else:
+        _launch("skinny_conv_kernel", _skinny_key(d, "fwd"), _conv1_flop(d),
+                lambda: C.conv1_fwd(ptr(x), ptr(w), ptr(y), ptr(stats), d, stream()))
+    return x, w, y, stats, d
+
+
 class Conv1Fn(Function):
     @staticmethod
     def forward(ctx, x, w, want_stats):
-        x, w = _check(x, "conv1 input"), _check(w, "conv1 weight")
-        n, c, h, wd = x.shape
-        d = _skinny_desc(n, c, h, wd, 0, cur_groups(want_stats))
-        y = torch.empty((n, d.hf, d.wf, 64), dtype=torch.float32, device=x.device)
-        stats = torch.empty((C.skinny_tiles(d), 128), dtype=torch.float32, device=x.device) if want_stats else None
-        C.conv1_fwd(ptr(x), ptr(w), ptr(y), ptr(stats), d, stream())
+        # (float images only: the backward's kernels have no byte form)
+        x, w, y, stats, d = _conv1_forward(_check(x, "conv1 input"), w, cur_groups(want_stats), want_stats)
         ctx.save_for_backward(x, w)
         ctx.desc = d
-        if stats is None:
-            stats = torch.empty(0, device=x.device)
-        ctx.mark_non_differentiable(stats)
-        ctx.set_materialize_grads(False)  # no zero tensor for the statistics output in backward
-        return y, stats
+        return y, _stats_output(ctx, stats, x.device)
 
     @staticmethod
     def backward(ctx, dy, _dstats):
@@ -270,6 +290,49 @@ def conv64_desc(n, hi, wi, stride, pad, transposed, groups=1):
     return Conv64Desc(n, hi, wi, ho, wo, 3, stride, pad, 1 if transposed else 0, groups)
 
 
+def _cached_pack(conv, slot, build):
+    """The kernel-layout copy `build()` of a frozen convolution's weights, kept on the module under `slot` and rebuilt only if the
+    parameter was moved or written (load_state_dict, .to(device))."""
+    key = (conv.weight.data_ptr(), conv.weight._version)
+    cached = getattr(conv, slot, None)
+    if cached is None or cached[0] != key:
+        cached = (key, build())
+        setattr(conv, slot, cached)
+    return cached[1]
+
+
+def _conv64_forward(x, w, bias, d, want_stats, x_bnp=None, frozen=None):
+    """y = conv(x) — or conv(relu(bn(x))) with x's BatchNorm record(s) x_bnp — for checked NHWC x and weights w [64, 64, 3, 3]
+    -> (y, per-tile statistics of y or None, packs, wino).  wino: conv3x3 stride 1 pad 1 on an even map (conv2, models/models.py:54;
+    layer1 of the ResNet trunk) runs as Winograd F(2x2, 3x3) — 16 multiplications per 2x2 output patch and (ci, co) instead of 36
+    (csrc/wino.hip), forward and data gradient; the weight gradient stays the direct contraction.  packs[0] / packs[1] are the
+    weights in that kernel's layout for the forward / the data gradient, packed on every call; with `frozen` (the module that owns
+    w) they are kept on the module instead, and the Winograd layout is packed for the forward alone."""
+    wino = bool(C.conv64_wino_supported(d))
+
+    def build():
+        packs = torch.empty((1 if (wino and frozen is not None) else 2, C.conv64_wino_packed_floats() if wino else C.conv64_packed_floats()),
+                            dtype=torch.float32, device=x.device)
+        back = ptr(packs[1]) if packs.shape[0] == 2 else None
+        if wino:
+            C.conv64_wino_pack_weights(ptr(w), ptr(packs[0]), back, stream())
+        else:
+            C.conv64_pack_weights(ptr(w), ptr(packs[0]), back, d, stream())
+        return packs
+    packs = build() if frozen is None else _cached_pack(frozen, "_srlz_pack_wino" if wino else "_srlz_pack64", build)
+    y = torch.empty((d.n, d.ho, d.wo, 64), dtype=torch.float32, device=x.device)
+    tiles = C.conv64_wino_tiles(d) if wino else C.conv64_fwd_tiles(d)
+    stats = torch.empty((tiles, 128), dtype=torch.float32, device=x.device) if want_stats else None
+    if wino:
+        name, fwd = "conv64_wino_kernel", C.conv64_wino_fwd
+    else:
+        pipe = bias is None and x_bnp is None and C.conv64_gather_pipe_supported(d, 0)
+        name, fwd = "conv64_gather_pipe_kernel" if pipe else "conv64_fwd_kernel", C.conv64_fwd
+    _launch(name, _conv64_key(d, "fwd"), _conv64_flop(d),
+            lambda: fwd(ptr(x), ptr(packs[0]), ptr(bias), ptr(y), ptr(stats), ptr(x_bnp), d, stream()))
+    return y, stats, packs, wino
+
+
 class PoolLink:
     """Hand-over between an encoder block (conv -> BatchNorm -> ReLU -> MaxPool, producer of a pooled map) and the convolution that
     consumes the pooled map: the consumer's data-gradient launch computes d(pooled) tile by tile and can take the two
@@ -296,34 +359,14 @@ class Conv64Fn(Function):
         n, hi, wi, ch = x.shape
         assert ch == 64 and tuple(w.shape) == (64, 64, 3, 3)
         d = conv64_desc(n, hi, wi, stride, pad, transposed, cur_groups(want_stats))
-        y = torch.empty((n, d.ho, d.wo, 64), dtype=torch.float32, device=x.device)
-        ctx.wino = bool(C.conv64_wino_supported(d))
-        if ctx.wino:
-            # conv3x3 stride 1 pad 1 on an even map (conv2, models/models.py:54): Winograd F(2x2, 3x3) — 16 multiplications per 2x2 output
-            # patch and (ci, co) instead of 36 (csrc/wino.hip), forward and data gradient; the weight gradient stays the direct contraction.
-            packs = torch.empty((2, C.conv64_wino_packed_floats()), dtype=torch.float32, device=x.device)  # (G g G^T, both directions)
-            C.conv64_wino_pack_weights(ptr(w), ptr(packs[0]), ptr(packs[1]), stream())
-            stats = torch.empty((C.conv64_wino_tiles(d), 128), dtype=torch.float32, device=x.device) if want_stats else None
-            _launch("conv64_wino_kernel", _conv64_key(d, "fwd"), _conv64_flop(d),
-                    lambda: C.conv64_wino_fwd(ptr(x), ptr(packs[0]), ptr(bias), ptr(y), ptr(stats), None, d, stream()))
-        else:
-            packs = torch.empty((2, C.conv64_packed_floats()), dtype=torch.float32, device=x.device)
-            C.conv64_pack_weights(ptr(w), ptr(packs[0]), ptr(packs[1]), d, stream())
-            stats = torch.empty((C.conv64_fwd_tiles(d), 128), dtype=torch.float32, device=x.device) if want_stats else None
-            name = "conv64_gather_pipe_kernel" if (bias is None and C.conv64_gather_pipe_supported(d, 0)) else "conv64_fwd_kernel"
-            _launch(name, _conv64_key(d, "fwd"), _conv64_flop(d),
-                    lambda: C.conv64_fwd(ptr(x), ptr(packs[0]), ptr(bias), ptr(y), ptr(stats), None, d, stream()))
+        y, stats, packs, ctx.wino = _conv64_forward(x, w, bias, d, want_stats)
         ctx.save_for_backward(x, packs)
         ctx.desc = d
         ctx.has_bias = bias is not None
         ctx.needs_dx = ctx.needs_input_grad[0]
         ctx.params = (w, bias)
         ctx.in_link = in_link  # (x is the pooled map of the block that filled this link)
-        if stats is None:
-            stats = torch.empty(0, device=x.device)
-        ctx.mark_non_differentiable(stats)
-        ctx.set_materialize_grads(False)  # no zero tensor for the statistics output in backward
-        return y, stats
+        return y, _stats_output(ctx, stats, x.device)
 
     @staticmethod
     def backward(ctx, dy, _dstats):
@@ -421,27 +464,53 @@ def _bn_params(stats, count, gamma, beta, running_mean, running_var, training, d
     return bnp, batch_stat
 
 
+def _bn_backward_sums_from_partials(partial, gb=(None, None), groups=1):
+    """The two BatchNorm-backward sums per group, dgamma and dbeta (of the parameters gb) from the per-tile partials that the epilogue
+    of a data-gradient kernel left (PoolLink, the decoder's fused backward kernels)."""
+    dev = partial.device
+    sums = torch.empty(128 * groups, dtype=torch.float32, device=dev)
+    dgamma = _gbuf(gb[0], 64, dev)
+    dbeta = _gbuf(gb[1], 64, dev)
+    nbytes = C.bn_bwd_workspace(0)
+    ws = _ws(nbytes, dev)
+    C.bn_bwd_finalize_partials(ptr(partial), partial.shape[0], groups, ptr(sums), ptr(dgamma), ptr(dbeta), ptr(ws), nbytes,
+                               stream())
+    return sums, dgamma, dbeta
+
+
+def pool_desc(n, h, w, pool_pad, out_nchw, groups):
+    """MaxPool2d(3, 2, pool_pad) over an [n, h, w, 64] map."""
+    return PoolDesc(n, h, w, (h + 2 * pool_pad - 3) // 2 + 1, (w + 2 * pool_pad - 3) // 2 + 1, pool_pad, 1 if out_nchw else 0, groups)
+
+
+def _bn_relu_pool(y, stats, bn, training, pool_pad, out_nchw, need_bwd, stat_sink, out_link):
+    """maxpool(relu(bn(y))) of a raw convolution output y (NHWC) with per-tile statistics `stats`, bn = (gamma, beta, running mean,
+    running var) -> (pooled, BatchNorm record, argmax bytes or None, pool descriptor).  The batch statistics go to stat_sink; with a
+    backward to come (need_bwd) the argmax is kept and an NHWC block leaves its record in out_link (PoolLink)."""
+    n, h, w, _ = y.shape
+    d = pool_desc(n, h, w, pool_pad, out_nchw, cur_groups(training))
+    bnp, batch_stat = _bn_params(stats, n * h * w, *bn, training, y.device)
+    if stat_sink is not None and batch_stat is not None:
+        stat_sink.append(batch_stat)
+    pooled = torch.empty((n, 64, d.hp, d.wp) if out_nchw else (n, d.hp, d.wp, 64), dtype=torch.float32, device=y.device)
+    argmax = torch.empty((n, d.hp, d.wp, 64), dtype=torch.uint8, device=y.device) if need_bwd else None
+    C.bn_relu_pool_fwd(ptr(y), ptr(bnp), ptr(pooled), ptr(argmax), d, stream())
+    if need_bwd and out_link is not None and not out_nchw:
+        out_link.record = (pooled, bnp, y, argmax, d)
+    return pooled, bnp, argmax, d
+
+
 class BNReLUPoolFn(Function):
     """y (raw conv output, NHWC) -> maxpool(relu(bn(y))).  `stats` are the conv's per-tile partial sums."""
 
     @staticmethod
     def forward(ctx, y, stats, gamma, beta, running_mean, running_var, training, pool_pad, out_nchw, stat_sink, out_link=None):
         y = _check(y, "bn input")
-        n, h, w, _ = y.shape
-        hp, wp = (h + 2 * pool_pad - 3) // 2 + 1, (w + 2 * pool_pad - 3) // 2 + 1
-        d = PoolDesc(n, h, w, hp, wp, pool_pad, 1 if out_nchw else 0, cur_groups(training))
-        bnp, batch_stat = _bn_params(stats, n * h * w, gamma, beta, running_mean, running_var, training, y.device)
-        if stat_sink is not None and batch_stat is not None:
-            stat_sink.append(batch_stat)
-        shape = (n, 64, hp, wp) if out_nchw else (n, hp, wp, 64)
-        pooled = torch.empty(shape, dtype=torch.float32, device=y.device)
         need_bwd = ctx.needs_input_grad[0] or ctx.needs_input_grad[2]
-        argmax = torch.empty((n, hp, wp, 64), dtype=torch.uint8, device=y.device) if need_bwd else None
-        C.bn_relu_pool_fwd(ptr(y), ptr(bnp), ptr(pooled), ptr(argmax), d, stream())
+        pooled, bnp, argmax, d = _bn_relu_pool(y, stats, (gamma, beta, running_mean, running_var), training, pool_pad, out_nchw,
+                                               need_bwd, stat_sink, out_link)
         if need_bwd:
             ctx.save_for_backward(y, bnp, argmax, pooled)
-            if out_link is not None and not out_nchw:
-                out_link.record = (pooled, bnp, y, argmax, d)
         ctx.desc, ctx.training, ctx.out_link = d, training, out_link
         ctx.params = (gamma, beta)
         return pooled
@@ -451,18 +520,15 @@ class BNReLUPoolFn(Function):
         y, bnp, argmax, pooled = ctx.saved_tensors
         dpooled = _check(dpooled, "pool grad")
         dy = torch.empty_like(y)
-        dgamma = _gbuf(ctx.params[0])
-        dbeta = _gbuf(ctx.params[1])
         part = ctx.out_link.take_partials() if ctx.out_link is not None else None
-        nbytes = C.bn_bwd_workspace(0)
-        ws = _ws(nbytes, y.device)
         if part is not None:  # the consumer's data gradient took the two sums in its epilogue (PoolLink)
-            sums = torch.empty(128 * max(ctx.desc.groups, 1), dtype=torch.float32, device=y.device)
-            C.bn_bwd_finalize_partials(ptr(part), part.shape[0], max(ctx.desc.groups, 1), ptr(sums), ptr(dgamma), ptr(dbeta), ptr(ws),
-                                       nbytes, stream())
+            sums, dgamma, dbeta = _bn_backward_sums_from_partials(part, ctx.params, max(ctx.desc.groups, 1))
             C.bn_relu_pool_bwd_apply(ptr(y), ptr(bnp), ptr(argmax), ptr(dpooled), ptr(sums), ptr(dy), 1 if ctx.training else 0,
                                      ctx.desc, stream())
         else:
+            dgamma, dbeta = _gbuf(ctx.params[0]), _gbuf(ctx.params[1])
+            nbytes = C.bn_bwd_workspace(0)
+            ws = _ws(nbytes, y.device)
             C.bn_relu_pool_bwd(ptr(y), ptr(bnp), ptr(argmax), ptr(dpooled), ptr(pooled), ptr(dy), ptr(dgamma), ptr(dbeta),
                                1 if ctx.training else 0, ptr(ws), nbytes, ctx.desc, stream())
         return dy, None, _give(ctx.params[0], dgamma), _give(ctx.params[1], dbeta), None, None, None, None, None, None, None
@@ -476,32 +542,12 @@ class EncInFn(Function):
 
     @staticmethod
     def forward(ctx, x, w, gamma, beta, running_mean, running_var, training, pool_pad, stat_sink, out_link=None):
-        u8 = is_u8_frames(x)  # the loader's bytes: normalised inside the kernels' window staging
-        x, w = (_check_u8(x, "conv1 input") if u8 else _check(x, "conv1 input")), _check(w, "conv1 weight")
-        n, c, h, wd = x.shape
-        d = _skinny_desc(n, c, h, wd, 0, cur_groups(training))
-        y = torch.empty((n, d.hf, d.wf, 64), dtype=torch.float32, device=x.device)
-        stats = torch.empty((C.skinny_tiles(d), 128), dtype=torch.float32, device=x.device) if training else None
-        if u8:
-            lut = norm_lut(x.device)
-            _launch("skinny_conv_kernel", _skinny_key(d, "fwd u8"), _conv1_flop(d),
-                    lambda: C.conv1_fwd_u8(ptr(x), ptr(lut), ptr(w), ptr(y), ptr(stats), d, stream()))
-        else:
-            _launch("skinny_conv_kernel", _skinny_key(d, "fwd"), _conv1_flop(d),
-                    lambda: C.conv1_fwd(ptr(x), ptr(w), ptr(y), ptr(stats), d, stream()))
-        hp, wp = (d.hf + 2 * pool_pad - 3) // 2 + 1, (d.wf + 2 * pool_pad - 3) // 2 + 1
-        pd = PoolDesc(n, d.hf, d.wf, hp, wp, pool_pad, 0, cur_groups(training))
-        bnp, batch_stat = _bn_params(stats, n * d.hf * d.wf, gamma, beta, running_mean, running_var, training, x.device)
-        if stat_sink is not None and batch_stat is not None:
-            stat_sink.append(batch_stat)
-        pooled = torch.empty((n, hp, wp, 64), dtype=torch.float32, device=x.device)
+        x, w, y, stats, d = _conv1_forward(x, w, cur_groups(training), training)
         need_bwd = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        argmax = torch.empty((n, hp, wp, 64), dtype=torch.uint8, device=x.device) if need_bwd else None
-        C.bn_relu_pool_fwd(ptr(y), ptr(bnp), ptr(pooled), ptr(argmax), pd, stream())
+        pooled, bnp, argmax, pd = _bn_relu_pool(y, stats, (gamma, beta, running_mean, running_var), training, pool_pad, False,
+                                                need_bwd, stat_sink, out_link)
         if need_bwd:
             ctx.save_for_backward(y, bnp, argmax, pooled, x, w)
-            if out_link is not None:
-                out_link.record = (pooled, bnp, y, argmax, pd)
         ctx.out_link = out_link
         ctx.desc, ctx.pdesc, ctx.training = d, pd, training
         ctx.params = (gamma, beta)
@@ -514,16 +560,14 @@ class EncInFn(Function):
         y, bnp, argmax, pooled, x, w = ctx.saved_tensors
         dpooled = _check(dpooled, "pool grad")
         dev = y.device
-        dgamma = _gbuf(ctx.params[0])
-        dbeta = _gbuf(ctx.params[1])
-        sums = torch.empty(128 * max(ctx.pdesc.groups, 1), dtype=torch.float32, device=dev)
-        nbytes = C.bn_bwd_workspace(0)
-        ws = _ws(nbytes, dev)
         part = ctx.out_link.take_partials() if ctx.out_link is not None else None
         if part is not None:  # conv2's data gradient took the two sums in its epilogue (PoolLink)
-            C.bn_bwd_finalize_partials(ptr(part), part.shape[0], max(ctx.pdesc.groups, 1), ptr(sums), ptr(dgamma), ptr(dbeta), ptr(ws),
-                                       nbytes, stream())
+            sums, dgamma, dbeta = _bn_backward_sums_from_partials(part, ctx.params, max(ctx.pdesc.groups, 1))
         else:
+            sums = torch.empty(128 * max(ctx.pdesc.groups, 1), dtype=torch.float32, device=dev)
+            dgamma, dbeta = _gbuf(ctx.params[0]), _gbuf(ctx.params[1])
+            nbytes = C.bn_bwd_workspace(0)
+            ws = _ws(nbytes, dev)
             C.bn_relu_pool_bwd_sums(ptr(y), ptr(bnp), ptr(argmax), ptr(dpooled), ptr(pooled), ptr(sums), ptr(dgamma), ptr(dbeta),
                                     ptr(ws), nbytes, ctx.pdesc, stream())
         dw = _gbuf(w)
@@ -611,18 +655,6 @@ def _bn_backward_for_producer(link, y_prev, bnp, da, training, partial=None, gb=
     return _bn_relu_backward(y_prev, bnp, da, training, gb)
 
 
-def _bn_backward_sums_from_partials(partial, gb=(None, None), groups=1):
-    dev = partial.device
-    sums = torch.empty(128 * groups, dtype=torch.float32, device=dev)
-    dgamma = _gbuf(gb[0], 64, dev)
-    dbeta = _gbuf(gb[1], 64, dev)
-    nbytes = C.bn_bwd_workspace(0)
-    ws = _ws(nbytes, dev)
-    C.bn_bwd_finalize_partials(ptr(partial), partial.shape[0], groups, ptr(sums), ptr(dgamma), ptr(dbeta), ptr(ws), nbytes,
-                               stream())
-    return sums, dgamma, dbeta
-
-
 def _operand_from(link, materialise=True):
     """(ctypes record or None, dy_out or None, keep-alive tuple) for the gradient arriving at a producer block.
     materialise: the record asks the data-gradient kernel to also store the rebuilt d(loss)/dy (dy_out) for a separate
@@ -653,32 +685,23 @@ class DecBlockFn(Function):
         n, hi, wi, _ = y_prev.shape
         bnp, _ = _bn_params(stats_prev, n * hi * wi, gamma, beta, running_mean, running_var, training, y_prev.device)
         d = conv64_desc(n, hi, wi, 2, 0, True, cur_groups(training))
-        packs = torch.empty((2, C.conv64_packed_floats()), dtype=torch.float32, device=y_prev.device)
-        C.conv64_pack_weights(ptr(w), ptr(packs[0]), ptr(packs[1]), d, stream())
-        y = torch.empty((n, d.ho, d.wo, 64), dtype=torch.float32, device=y_prev.device)
-        stats = torch.empty((C.conv64_fwd_tiles(d), 128), dtype=torch.float32, device=y_prev.device) if want_stats else None
-        _launch("conv64_fwd_kernel", _conv64_key(d, "fwd"), _conv64_flop(d),
-                lambda: C.conv64_fwd(ptr(y_prev), ptr(packs[0]), ptr(bias), ptr(y), ptr(stats), ptr(bnp), d, stream()))
+        y, stats, packs, _ = _conv64_forward(y_prev, w, bias, d, want_stats, bnp)
         ctx.save_for_backward(y_prev, bnp, packs)
         ctx.desc, ctx.training = d, training
         ctx.in_link, ctx.out_link = in_link, out_link
         ctx.params = (gamma, beta, w, bias)
-        if stats is None:
-            stats = torch.empty(0, device=y_prev.device)
-        ctx.mark_non_differentiable(stats)
-        ctx.set_materialize_grads(False)  # no zero tensor for the statistics output in backward
-        return y, stats
+        return y, _stats_output(ctx, stats, y_prev.device)
 
     @staticmethod
     def backward(ctx, dy, _dstats):
         y_prev, bnp, packs = ctx.saved_tensors
         d = ctx.desc
         dy = _check(dy, "decoder block dy")
+        da = torch.empty_like(y_prev)
         if ctx.out_link is not None and ctx.out_link.record is not None and C.conv64_bwd_fused_supported(d):
             # `dy` is dA of the following BatchNorm+ReLU: ONE kernel rebuilds the true dy while staging it and contracts it both ways
             # (data gradient and weight / bias gradient) — it is never written to memory
             dy_bn, _, keep = _operand_from(ctx.out_link, materialise=False)
-            da = torch.empty_like(y_prev)
             dw = _gbuf(ctx.params[2])
             db = _gbuf(ctx.params[3], 64, dy.device)
             nbytes = C.conv64_bwd_fused_workspace(d)
@@ -688,26 +711,24 @@ class DecBlockFn(Function):
             _launch("conv64_bwd_fused_kernel", _conv64_key(d, "dgrad+wgrad"), 2.0 * _conv64_flop(d),
                     lambda: C.conv64_bwd_fused(ptr(y_prev), ptr(bnp), ptr(dy), dy_bn, ptr(packs[1]), ptr(da), ptr(dw), ptr(db), ptr(part),
                                                ptr(ws), nbytes, d, stream()))
-            dy_prev, dgamma, dbeta = _bn_backward_for_producer(ctx.in_link, y_prev, bnp, da, ctx.training, partial=part, gb=ctx.params[:2])
-            gp, bp, wp, cp = ctx.params
-            return dy_prev, None, _give(gp, dgamma), _give(bp, dbeta), None, None, None, _give(wp, dw), _give(cp, db), None, None, None
-        # dy_bn not None: `dy` is dA of the following BatchNorm+ReLU; the data-gradient kernel rebuilds the true dy in its
-        # operand load and stores it (dy_true) for the weight-gradient kernel, which therefore runs second
-        dy_bn, dy_true, keep = _operand_from(ctx.out_link)
-        da = torch.empty_like(y_prev)
-        # (the fused-operand launch is a different instantiation of the kernel: timed under its own name)
-        _launch("conv64_fwd_kernel" if dy_bn is None else "conv64_fwd_kernel<bn-bwd operand>", _conv64_key(d, "dgrad"),
-                _conv64_flop(d), lambda: C.conv64_bwd_data(ptr(dy), ptr(packs[1]), ptr(da), dy_bn, d, stream()))
-        if dy_true is not None:
-            dy = dy_true
-        dw = _gbuf(ctx.params[2])
-        db = _gbuf(ctx.params[3], 64, dy.device)
-        nbytes = C.conv64_bwd_weight_workspace(d)
-        ws = _ws(nbytes, dy.device, slot=1)
-        _launch("conv64_wgrad_kernel", _conv64_key(d, "wgrad"), _conv64_flop(d),
-                lambda: C.conv64_bwd_weight(ptr(y_prev), ptr(dy), ptr(dw), ptr(db), ptr(bnp), None, ptr(ws), nbytes, d,
-                                            stream()))
-        dy_prev, dgamma, dbeta = _bn_backward_for_producer(ctx.in_link, y_prev, bnp, da, ctx.training, gb=ctx.params[:2])
+        else:
+            # dy_bn not None: `dy` is dA of the following BatchNorm+ReLU; the data-gradient kernel rebuilds the true dy in its
+            # operand load and stores it (dy_true) for the weight-gradient kernel, which therefore runs second
+            dy_bn, dy_true, keep = _operand_from(ctx.out_link)
+            # (the fused-operand launch is a different instantiation of the kernel: timed under its own name)
+            _launch("conv64_fwd_kernel" if dy_bn is None else "conv64_fwd_kernel<bn-bwd operand>", _conv64_key(d, "dgrad"),
+                    _conv64_flop(d), lambda: C.conv64_bwd_data(ptr(dy), ptr(packs[1]), ptr(da), dy_bn, d, stream()))
+            if dy_true is not None:
+                dy = dy_true
+            dw = _gbuf(ctx.params[2])
+            db = _gbuf(ctx.params[3], 64, dy.device)
+            nbytes = C.conv64_bwd_weight_workspace(d)
+            ws = _ws(nbytes, dy.device, slot=1)
+            _launch("conv64_wgrad_kernel", _conv64_key(d, "wgrad"), _conv64_flop(d),
+                    lambda: C.conv64_bwd_weight(ptr(y_prev), ptr(dy), ptr(dw), ptr(db), ptr(bnp), None, ptr(ws), nbytes, d,
+                                                stream()))
+            part = None
+        dy_prev, dgamma, dbeta = _bn_backward_for_producer(ctx.in_link, y_prev, bnp, da, ctx.training, partial=part, gb=ctx.params[:2])
         gp, bp, wp, cp = ctx.params
         return dy_prev, None, _give(gp, dgamma), _give(bp, dbeta), None, None, None, _give(wp, dw), _give(cp, db), None, None, None
 
@@ -716,17 +737,22 @@ class DecBlockFn(Function):
 # shape is supported (C = 3 / 6); the two-launch form serves hotpath.TAPS (no link) and is the reference of the fused kernel's tests.
 
 
+def _dec_out_open(y_prev, stats_prev, bn, training, w):
+    """What both forms of the last ConvTranspose start with: the checked (y_prev, w), the BatchNorm record of y_prev from its per-tile
+    statistics and bn = (gamma, beta, running mean, running var), and the descriptor of ConvTranspose2d(64, C, 4, 2) over y_prev's map."""
+    y_prev, w = _check(y_prev, "decoder output input"), _check(w, "convT_out weight")
+    n, hf, wf, _ = y_prev.shape
+    bnp, _ = _bn_params(stats_prev, n * hf * wf, *bn, training, y_prev.device)
+    return y_prev, w, bnp, SkinnyDesc(n, w.shape[1], (hf - 1) * 2 + 4, (wf - 1) * 2 + 4, hf, wf, 1, cur_groups(training))
+
+
 class DecOutFn(Function):
     """(y_prev raw, stats, BN params) -> ConvTranspose2d(64, C, 4, 2)(relu(bn(y_prev))), NCHW (models/models.py:79-82)."""
 
     @staticmethod
     def forward(ctx, y_prev, stats_prev, gamma, beta, running_mean, running_var, training, w, bias, in_link=None):
-        y_prev, w = _check(y_prev, "decoder output input"), _check(w, "convT_out weight")
-        n, hf, wf, _ = y_prev.shape
-        bnp, _ = _bn_params(stats_prev, n * hf * wf, gamma, beta, running_mean, running_var, training, y_prev.device)
-        c = w.shape[1]
-        d = SkinnyDesc(n, c, (hf - 1) * 2 + 4, (wf - 1) * 2 + 4, hf, wf, 1, cur_groups(training))
-        y = torch.empty((n, c, d.himg, d.wimg), dtype=torch.float32, device=y_prev.device)
+        y_prev, w, bnp, d = _dec_out_open(y_prev, stats_prev, (gamma, beta, running_mean, running_var), training, w)
+        y = torch.empty((d.n, d.c, d.himg, d.wimg), dtype=torch.float32, device=y_prev.device)
         _launch("convT_out_os_kernel", _skinny_key(d, "fwd"), _convT_out_flop(d),
                 lambda: C.convT_out_fwd(ptr(y_prev), ptr(w), ptr(bias), ptr(y), ptr(bnp), d, stream()))
         ctx.save_for_backward(y_prev, bnp, w)
@@ -787,17 +813,13 @@ class DecOutLossFn(Function):
 
     @staticmethod
     def forward(ctx, y_prev, stats_prev, gamma, beta, running_mean, running_var, training, w, bias, in_link, target, mean):
-        y_prev, w = _check(y_prev, "decoder output input"), _check(w, "convT_out weight")
         u8 = is_u8_frames(target)
         target = _check_u8(target, "reconstruction target") if u8 else _check(target, "reconstruction target")
-        n, hf, wf, _ = y_prev.shape
-        bnp, _ = _bn_params(stats_prev, n * hf * wf, gamma, beta, running_mean, running_var, training, y_prev.device)
-        c = w.shape[1]
-        d = SkinnyDesc(n, c, (hf - 1) * 2 + 4, (wf - 1) * 2 + 4, hf, wf, 1, cur_groups(training))
-        if tuple(target.shape) != (n, c, d.himg, d.wimg) or n % 2:
+        y_prev, w, bnp, d = _dec_out_open(y_prev, stats_prev, (gamma, beta, running_mean, running_var), training, w)
+        if tuple(target.shape) != (d.n, d.c, d.himg, d.wimg) or d.n % 2:
             raise C.SrlzError("fused reconstruction loss: target %s does not match the decoder output %s"
-                              % (tuple(target.shape), (n, c, d.himg, d.wimg)))
-        err = torch.empty((n, c, d.himg, d.wimg), dtype=torch.float32, device=y_prev.device)
+                              % (tuple(target.shape), (d.n, d.c, d.himg, d.wimg)))
+        err = torch.empty((d.n, d.c, d.himg, d.wimg), dtype=torch.float32, device=y_prev.device)
         nwg = C.convT_out_fwd_loss_workgroups(d)
         part = _ws(2 * nwg * 8, y_prev.device, slot=2)
         if u8:
@@ -1077,7 +1099,6 @@ class TotalLossFn(Function):
 
     @staticmethod
     def forward(ctx, weights, tail, *losses):
-        import ctypes
         n = len(losses)
         losses = [_check(l, "loss term").reshape(()) for l in losses]
         ptrs = (ctypes.c_void_p * n)(*[l.data_ptr() for l in losses])
@@ -1118,6 +1139,7 @@ class MaskColumnsFn(Function):
 
 
 _param_tables = {}
+_grad_tables = {}
 
 
 def _param_table(params):
@@ -1167,9 +1189,6 @@ class ParamNormFn(Function):
         C.param_norms_grad(ptr(ptrs), ptr(gptrs), ptr(lens), len(params), ctx.mode, ptr(norms), ptr(dout), ctx.scale,
                            stream())
         return (None,) + tuple(_give(p, g) for p, g in zip(params, grads))
-
-
-_grad_tables = {}
 
 
 class ToNHWCFn(Function):
@@ -1314,7 +1333,6 @@ class FanOutFn(Function):
 
     @staticmethod
     def backward(ctx, *grads):
-        import ctypes
         terms = [_check(g, "fan-out gradient") for g in grads if g is not None]
         if not terms:
             return None, None
