@@ -9,7 +9,7 @@
  *
  * Conventions
  *   - plain C types only; every pointer is a DEVICE pointer unless the name ends in _host.
- *   - all floating point data is fp32 (only srlz_knn_f64, the evaluation search, and srlz_pca_*, the PCA baseline, take fp64); activations are NHWC ([N][H][W][C], C fastest) unless stated NCHW.
+ *   - all floating point data is fp32 (only srlz_knn_f64, the evaluation search, srlz_gtc_rows_f64, the ground-truth correlation, and srlz_pca_*, the PCA baseline, take fp64); activations are NHWC ([N][H][W][C], C fastest) unless stated NCHW.
  *     The reference's tensors are NCHW ([B,C,D1,D2]; D1/D2 are the image's W/H because the loader transposes,
  *     preprocessing/data_loader.py:255); the NCHW<->NHWC change happens INSIDE conv1 (reads NCHW) and the last
  *     ConvTranspose (writes NCHW), so callers only ever hand over / receive reference-layout images.
@@ -695,6 +695,27 @@ int srlz_dropout_bwd(const float* dy, const unsigned char* mask, float keep, flo
 size_t srlz_knn_workspace(int N, int Q, int D, int K);
 int srlz_knn_f64(const double* db /*[N,D]*/, int N, const double* queries /*[Q,D]*/, int Q, int D, int K, int* idx /*[Q,K]*/,
                  double* dist2 /*[Q,K]*/, void* ws, size_t ws_bytes, srlz_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Evaluation: ground-truth correlation (GTC) in fp64 (csrc/gtc.hip).  Replaces
+ *   corr = np.corrcoef(x=x + eps, y=states_rewards['states'] + eps, rowvar=0)                plotting/representation_plot.py:283
+ * of which the reference reads rows 0 .. G-1 only (:296-300: the diagonal entry zeroed, max(abs(row)) per ground-truth dimension).
+ * gt [N, G] and states [N, S] are fp64 (float32 states convert exactly); column k of the virtual matrix [gt | states] is gt[:, k]
+ * for k < G and states[:, k - G] behind it — the concatenation is never written.
+ *   Two passes: mean_k = sum_r col_k[r] / N, then var_k = sum_r (col_k[r] - mean_k)^2 / (N - 1) for all G + S columns and
+ *   cov_{g,k} = sum_r (gt_g[r] - mean_g)(col_k[r] - mean_k) / (N - 1) for g < G — never sum x^2 - (sum x)^2 / N.
+ *   corr[g][k] = cov_{g,k} / sqrt(var_g) / sqrt(var_k) (two divisions, as numpy), then clipped to [-1, 1].  A zero-variance column
+ *   gives 0 / 0 = NaN in its entries exactly where numpy does (NaN survives the clip); nothing is raised for it.
+ *   colstats [2, G + S]: row 0 the means, row 1 the variances (ddof 1).
+ *   Rows are cut into chunks whose size is a function of (N, G, S) alone; each chunk's partial sums go to ws and are added in chunk
+ *   order.  No float atomics, every sum has one order: repeated calls are bit-identical, whatever number of workgroups ran at once.
+ * N >= 2, 1 <= G <= 16, S >= 1, N * (G + S) below 2^31; anything else is SRLZ_ERR_BAD_DESC, a null pointer SRLZ_ERR_NULL,
+ * ws_bytes < srlz_gtc_workspace(N, G, S) SRLZ_ERR_WORKSPACE — all before any launch.  srlz_gtc_workspace returns 0 for a shape the
+ * launcher rejects.
+ * ------------------------------------------------------------------------------------------------------------ */
+size_t srlz_gtc_workspace(int N, int G, int S);
+int srlz_gtc_rows_f64(const double* gt /*[N,G]*/, const double* states /*[N,S]*/, int N, int G, int S, double* corr /*[G,G+S]*/,
+                      double* colstats /*[2,G+S]: mean, variance (ddof 1)*/, void* ws, size_t ws_bytes, srlz_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * PCA baseline: sklearn's IncrementalPCA in fp64 through a Gram matrix (csrc/pca.hip).  Replaces, per minibatch,

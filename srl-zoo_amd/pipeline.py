@@ -1,7 +1,7 @@
-"""The three helpers train.py imports from the reference's pipeline.py (getLogFolderName :28-51, saveConfig :223-236,
-correlationCall) plus the exit-code constants (:23-25), the KNN-MSE evaluation call with its two helpers (knnCall :194-220,
-createGroundTruthFolder :166-177, useRelativePosition :239-246) and the PCA baseline call (pcaCall :150-163).  The grid-search driver
-itself is out of scope."""
+"""The helpers train.py imports from the reference's pipeline.py (getLogFolderName :28-51, saveConfig :223-236, correlationCall
+:180-191) plus the exit-code constants (:23-25), the KNN-MSE evaluation call with its two helpers (knnCall :194-220,
+createGroundTruthFolder :166-177, useRelativePosition :239-246) and the PCA baseline call (pcaCall :150-163).  Every evaluation runs
+in a fresh child of this interpreter.  The grid-search driver itself is out of scope."""
 from __future__ import print_function, division
 
 import datetime
@@ -12,7 +12,7 @@ import sys
 from collections import OrderedDict
 from pprint import pprint
 
-from utils import printBlue, printGreen, printRed, printYellow, createFolder
+from utils import printBlue, printGreen, printRed, createFolder
 
 MATPLOTLIB_WARNING_CODE = -11
 NO_PAIRS_ERROR = 10  # no dissimilar/reference pairs found (robotic priors)
@@ -43,10 +43,23 @@ def saveConfig(exp_config, print_config=False):
     print("Saved config to log folder: {}".format(exp_config['log-folder']))
 
 
+def correlationArguments(exp_config, plot=False):
+    """The reference's argument list for plotting.representation_plot (pipeline.py:186-190)."""
+    log_folder = exp_config["log-folder"] + "/states_rewards.npz"
+    data_folder = 'data/' + exp_config['data-folder']
+    use_plot = [] if plot else ["--print-corr"]
+    return ["-i", log_folder, "--data-folder", data_folder, "--correlation"] + use_plot
+
+
 def correlationCall(exp_config, plot=False):
-    """The reference shells out to plotting.representation_plot for the ground-truth correlation; plotting and
-    evaluation are outside this build's scope, so this only says so."""
-    printYellow("correlationCall: ground-truth correlation (plotting/) is out of scope of the MI355X hot-path build")
+    """Ground-truth correlation of the representation in exp_config['log-folder'] (reference pipeline.py:180-191; writes
+    gt_correlation.json there): plotting.representation_plot in a fresh child process — this interpreter, as knnCall starts its
+    child.  No figure is drawn whatever `plot` says.
+    :param exp_config: (dict)
+    :param plot: (bool)"""
+    ok = subprocess.call([sys.executable, '-m', 'plotting.representation_plot'] + correlationArguments(exp_config, plot),
+                         env=_childEnv())
+    printConfigOnError(ok, exp_config, "correlationCall")
 
 
 def printConfigOnError(return_code, exp_config, step_name):

@@ -193,6 +193,8 @@ _PROTOS = {
     "srlz_episode_prior_bwd": (c_int, [P, P, P, P, c_int, c_int, P, P, P, P, c_size_t, P, P, P, P, P, P, P, P]),
     "srlz_knn_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
     "srlz_knn_f64": (c_int, [P, c_int, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
+    "srlz_gtc_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "srlz_gtc_rows_f64": (c_int, [P, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "srlz_pca_workspace": (c_size_t, [c_int, c_int]),
     "srlz_pca_transform_workspace": (c_size_t, [c_int, c_int, c_int]),
     "srlz_pca_stats": (c_int, [P, P, P, c_int, c_int, c_int, c_longlong, P, P, P, P, P]),

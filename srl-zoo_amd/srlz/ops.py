@@ -1805,18 +1805,18 @@ class ConcatOneHotFn(Function):
         return dcat[:, :ctx.sdim].contiguous(), None, None
 
 
-def _knn_host_array(a, name):
+def _eval_host_array(a, name, who="knn"):
     """numpy / torch, float32 / float64, 2-D, finite -> C-contiguous float64 numpy (an exact conversion)."""
     import numpy as np
     if torch.is_tensor(a):
         a = a.detach().cpu().numpy()
     a = np.asarray(a)
     if a.dtype not in (np.float32, np.float64):
-        raise ValueError("knn: %s must be float32 or float64 (got %s)" % (name, a.dtype))
+        raise ValueError("%s: %s must be float32 or float64 (got %s)" % (who, name, a.dtype))
     if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
-        raise ValueError("knn: %s must be a non-empty [rows, D] array (got shape %s)" % (name, a.shape))
+        raise ValueError("%s: %s must be a non-empty [rows, D] array (got shape %s)" % (who, name, a.shape))
     if not np.isfinite(a).all():
-        raise ValueError("knn: %s holds NaN or infinite values" % name)
+        raise ValueError("%s: %s holds NaN or infinite values" % (who, name))
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
@@ -1830,8 +1830,8 @@ def knn(db, k, queries=None):
     :return: (idx int64 [Q, k], dist2 float64 [Q, k]) as CPU numpy — SQUARED distances.
     ValueError: non-finite input, mismatched D, k outside [1, min(32, N)].  RuntimeError without a GPU: there is no CPU fallback."""
     import numpy as np
-    dbh = _knn_host_array(db, "db")
-    qh = dbh if queries is None else _knn_host_array(queries, "queries")
+    dbh = _eval_host_array(db, "db")
+    qh = dbh if queries is None else _eval_host_array(queries, "queries")
     if qh.shape[1] != dbh.shape[1]:
         raise ValueError("knn: queries have D = %d, the database D = %d" % (qh.shape[1], dbh.shape[1]))
     k = int(k)
@@ -1852,6 +1852,43 @@ def knn(db, k, queries=None):
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
     C.knn_f64(ptr(db_d), n, ptr(q_d), nq, d, k, ptr(idx), ptr(dist2), ptr(ws), nbytes, stream())
     return idx.cpu().numpy().astype(np.int64), dist2.cpu().numpy()
+
+
+GTC_MAX_G = 16  # include/srlz.h, srlz_gtc_rows_f64
+
+
+def gt_correlation(gt, states):
+    """Rows 0 .. G-1 of np.corrcoef(gt, states, rowvar=0): the correlation of every ground-truth dimension with all G + S columns of
+    [gt | states] — the rows the reference's plotCorrelation reads (plotting/representation_plot.py:283, :296-300) — by the two-pass
+    fp64 kernels of csrc/gtc.hip.  gt [N, G] and states [N, S]: host arrays (numpy or torch), float32 or float64, uploaded as fp64.
+    A zero-variance column gives NaN where numpy gives NaN; nothing is raised for it.
+    :return: corr float64 [G, G + S] as CPU numpy
+    ValueError: non-finite input, mismatched N, N < 2, G outside [1, 16], S < 1, N * (G + S) >= 2^31.  RuntimeError without a GPU:
+    there is no CPU fallback."""
+    gth = _eval_host_array(gt, "gt", "gt_correlation")
+    sth = _eval_host_array(states, "states", "gt_correlation")
+    n, g = gth.shape
+    s = sth.shape[1]
+    if sth.shape[0] != n:
+        raise ValueError("gt_correlation: gt has %d rows, states %d" % (n, sth.shape[0]))
+    if n < 2:
+        raise ValueError("gt_correlation: needs N >= 2 rows (N = %d)" % n)
+    if g > GTC_MAX_G:
+        raise ValueError("gt_correlation: G must lie in [1, %d] (G = %d)" % (GTC_MAX_G, g))
+    if n * (g + s) >= 2 ** 31:
+        raise ValueError("gt_correlation: N * (G + S) must stay below 2^31 (N = %d, G = %d, S = %d)" % (n, g, s))
+    if not torch.cuda.is_available():
+        raise C.SrlzError("gt_correlation runs on the GPU only (torch.cuda.is_available() is False): the srl-zoo_amd build has no "
+                          "CPU fallback")
+    device = torch.device("cuda", torch.cuda.current_device())
+    gt_d = torch.from_numpy(gth).to(device)
+    st_d = torch.from_numpy(sth).to(device)
+    corr = torch.empty((g, g + s), dtype=torch.float64, device=device)
+    colstats = torch.empty((2, g + s), dtype=torch.float64, device=device)
+    nbytes = C.gtc_workspace(n, g, s)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+    C.gtc_rows_f64(ptr(gt_d), ptr(st_d), n, g, s, ptr(corr), ptr(colstats), ptr(ws), nbytes, stream())
+    return corr.cpu().numpy()
 
 
 def normalize_u8(frames, out=None):

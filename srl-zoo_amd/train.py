@@ -6,7 +6,8 @@ environment; backend "nccl" is RCCL on ROCm).
 --model-type custom_cnn, mlp and linear run (mlp / linear without a split representation, perceptual or triplet), as do the
 reward-prior and episode-prior losses (--balanced-sampling selects the episode prior's balanced partner draw).
 Out of scope of this build (rejected with a clear message): --model-type resnet, the robotic-priors loss (priors), reward-prior /
-episode-prior combined with triplet, plots.
+episode-prior combined with triplet, plots.  After the run rank 0 evaluates the ground-truth correlation of the learned states
+(pipeline.correlationCall -> plotting.representation_plot on csrc/gtc.hip, in a child process): gt_correlation.json in the log folder.
 """
 from __future__ import print_function, division, absolute_import
 
