@@ -9,7 +9,7 @@
  *
  * Conventions
  *   - plain C types only; every pointer is a DEVICE pointer unless the name ends in _host.
- *   - all floating point data is fp32 (only srlz_knn_f64, the evaluation search, srlz_gtc_rows_f64, the ground-truth correlation, and srlz_pca_*, the PCA baseline, take fp64); activations are NHWC ([N][H][W][C], C fastest) unless stated NCHW.
+ *   - all floating point data is fp32 (only srlz_knn_f64, the evaluation search, srlz_gtc_rows_f64, the ground-truth correlation, and srlz_pca_*, the PCA baseline, take fp64; srlz_reward_probe_* return their loss sums in fp64); activations are NHWC ([N][H][W][C], C fastest) unless stated NCHW.
  *     The reference's tensors are NCHW ([B,C,D1,D2]; D1/D2 are the image's W/H because the loader transposes,
  *     preprocessing/data_loader.py:255); the NCHW<->NHWC change happens INSIDE conv1 (reads NCHW) and the last
  *     ConvTranspose (writes NCHW), so callers only ever hand over / receive reference-layout images.
@@ -716,6 +716,43 @@ int srlz_knn_f64(const double* db /*[N,D]*/, int N, const double* queries /*[Q,D
 size_t srlz_gtc_workspace(int N, int G, int S);
 int srlz_gtc_rows_f64(const double* gt /*[N,G]*/, const double* states /*[N,S]*/, int N, int G, int S, double* corr /*[G,G+S]*/,
                       double* colstats /*[2,G+S]: mean, variance (ddof 1)*/, void* ws, size_t ws_bytes, srlz_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Evaluation: the reward-prediction probe (csrc/reward_probe.hip).  Replaces the minibatch loop of
+ *   outputs = model.rewardModel(inputs, next_inputs); _, preds = th.max(outputs, dim=1); loss = criterion(outputs, labels);
+ *   loss.backward(); optimizer.step(); running_loss += ...; corrects[...] += ...          evaluation/predict_reward.py:106-141
+ * with the classifier Linear(2S,4)-ReLU-Linear(4,4)-ReLU-Linear(4,2) on th.cat((state, next_state), dim=1)
+ *                                                                                         models/forward_inverse.py:78-95
+ * by ONE launch per training phase (srlz_reward_probe_fit) and ONE per validation phase (srlz_reward_probe_eval).
+ *   states [N, S] fp32 and labels [N] int32 (class 1 where the label is 1, class 0 otherwise) stay on the device for the whole run.
+ *   idx [n, B] int32 on the device, idx_host the SAME table on the host: every entry is checked there against [0, N - 2] before
+ *   anything is launched (SRLZ_ERR_BAD_DESC).  Row b of minibatch s is the 2S floats at states + idx[s][b] * S, i.e. the rows i and
+ *   i + 1 — the concatenation is never written.
+ *   params / m / v: 4 * 2S + 34 floats each in state_dict order (reward_net.0.weight [4, 2S], 0.bias, 2.weight [4, 4], 2.bias,
+ *   4.weight [2, 4], 4.bias).
+ *   running_loss [1] fp64 and counts [5] int64 (correct, correct of class 0, of class 1, rows of class 0, of class 1) are ADDED TO:
+ *   the caller zeroes them where a phase begins.  Argmax ties go to class 0, as th.max does.
+ * fit: n_steps consecutive Adam steps (torch's defaults are the caller's to pass; no weight decay, no amsgrad; the arithmetic of
+ *   srlz_adam_step) by one workgroup that keeps params, m and v in LDS from the first step to the last.  Step s uses the bias
+ *   corrections of t = t0 + s + 1 (t0: the Adam steps already taken).  Forward in fp32, cross-entropy as the mean over B in
+ *   log-sum-exp form, every sum over rows in one order that depends on (S, B) alone (rows are processed in chunks of
+ *   srlz_reward_probe_chunk_rows(S)), running_loss += (sum of the row losses / B) * B per step in fp64.  step_loss (may be NULL)
+ *   receives the n_steps mean losses in fp64.  No float atomics; n_steps in one call and n_steps calls of one step leave the same
+ *   bits in params, m, v, running_loss and counts.  S must lie in [1, 512] (SRLZ_ERR_BAD_DESC): four copies of the parameters and
+ *   a row chunk have to fit in LDS.
+ * eval: the same forward over n_batches * B independent rows by many workgroups, the row loss in fp64; per-workgroup sums go to
+ *   ws (srlz_reward_probe_eval_workspace(n_batches, B) bytes) and are added in workgroup order by the workgroup that finishes
+ *   last (`ticket`: one zeroed unsigned the kernel leaves zeroed, as in srlz_episode_prior_fwd).  params are only read.
+ * ------------------------------------------------------------------------------------------------------------ */
+int srlz_reward_probe_chunk_rows(int S); /* rows of a chunk; 0 for an S the launchers reject */
+int srlz_reward_probe_fit(const float* states /*[N,S]*/, const int* labels /*[N]*/, int N, int S, const int* idx /*[n_steps,B]*/,
+                          const int* idx_host /*[n_steps,B]*/, int n_steps, int B, float* params, float* m, float* v, int t0, double lr,
+                          double beta1, double beta2, double eps, double* running_loss /*[1]*/, long long* counts /*[5]*/,
+                          double* step_loss /*[n_steps] or NULL*/, srlz_stream_t stream);
+size_t srlz_reward_probe_eval_workspace(int n_batches, int B);
+int srlz_reward_probe_eval(const float* states /*[N,S]*/, const int* labels /*[N]*/, int N, int S, const int* idx /*[n_batches,B]*/,
+                           const int* idx_host /*[n_batches,B]*/, int n_batches, int B, const float* params, double* running_loss /*[1]*/,
+                           long long* counts /*[5]*/, void* ws, size_t ws_bytes, unsigned* ticket, srlz_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * PCA baseline: sklearn's IncrementalPCA in fp64 through a Gram matrix (csrc/pca.hip).  Replaces, per minibatch,

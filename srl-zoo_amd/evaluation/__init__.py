@@ -1,3 +1,4 @@
 """Evaluation of a learned representation (reference evaluation/): KNN-MSE on the exact HIP k-nearest-neighbour search
-(knn_images), the states of a trained model on another dataset (predict_dataset) and the results table of a folder of
-experiments (gather_results).  Plots are out of scope of this build."""
+(knn_images), the states of a trained model on another dataset (predict_dataset), the results table of a folder of
+experiments (gather_results) and the reward-prediction probe on its one-launch-per-phase kernels (predict_reward).  Plots are
+out of scope of this build."""

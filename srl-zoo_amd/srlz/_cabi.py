@@ -195,6 +195,11 @@ _PROTOS = {
     "srlz_knn_f64": (c_int, [P, c_int, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
     "srlz_gtc_workspace": (c_size_t, [c_int, c_int, c_int]),
     "srlz_gtc_rows_f64": (c_int, [P, P, c_int, c_int, c_int, P, P, P, c_size_t, P]),
+    "srlz_reward_probe_chunk_rows": (c_int, [c_int]),
+    "srlz_reward_probe_fit": (c_int, [P, P, c_int, c_int, P, P, c_int, c_int, P, P, P, c_int, c_double, c_double, c_double, c_double, P,
+                                      P, P, P]),
+    "srlz_reward_probe_eval_workspace": (c_size_t, [c_int, c_int]),
+    "srlz_reward_probe_eval": (c_int, [P, P, c_int, c_int, P, P, c_int, c_int, P, P, P, P, c_size_t, P, P]),
     "srlz_pca_workspace": (c_size_t, [c_int, c_int]),
     "srlz_pca_transform_workspace": (c_size_t, [c_int, c_int, c_int]),
     "srlz_pca_stats": (c_int, [P, P, P, c_int, c_int, c_int, c_longlong, P, P, P, P, P]),
@@ -227,7 +232,7 @@ _NOT_STATUS = {"srlz_version", "srlz_device_cus", "srlz_conv64_fwd_tiles", "srlz
                "srlz_conv64_bwd_data_tiles", "srlz_conv64_bwd_fused_bn_rows", "srlz_conv64_wino_supported", "srlz_conv64_wino_packed_floats",
                "srlz_conv64_wino_tiles", "srlz_conv64_wino_bwd_data_rows",
                "srlz_conv64_debug_program", "srlz_comm_world", "srlz_dense_supported",
-               "srlz_dense_out_fwd_loss_workgroups"}
+               "srlz_dense_out_fwd_loss_workgroups", "srlz_reward_probe_chunk_rows"}
 
 EXPORTED = sorted(_PROTOS.keys())
 

@@ -1891,6 +1891,129 @@ def gt_correlation(gt, states):
     return corr.cpu().numpy()
 
 
+REWARD_PROBE_MAX_S = 512  # include/srlz.h, srlz_reward_probe_fit: the parameters and their Adam moments stay in LDS
+REWARD_PROBE_COUNTS = ("correct", "correct_0", "correct_1", "rows_0", "rows_1")  # the five int64 counters, in this order
+_REWARD_PROBE_TICKET = {}
+
+
+class RewardProbeData(object):
+    """The dataset of the reward probe on the device: states fp32 [N, S] and labels int32 [N] (reward_probe_data)."""
+
+    def __init__(self, states, labels):
+        self.states, self.labels = states, labels
+        self.n, self.s = int(states.shape[0]), int(states.shape[1])
+
+
+def reward_probe_data(states, labels):
+    """states [N, S] (host array, numpy or torch, float32 or float64, finite) and labels [N] (integers in {0, 1}) -> RewardProbeData,
+    validated here on the host ONCE and uploaded for the whole run: the kernels never see a label they cannot count.
+    ValueError: shapes, a non-integer label array, a label outside {0, 1}, S outside [1, 512].  SrlzError without a GPU."""
+    import numpy as np
+    sth = _eval_host_array(states, "states", "reward_probe")
+    lab = labels.detach().cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+    if lab.dtype.kind not in "iu":
+        raise ValueError("reward_probe: labels must be integers (got %s)" % lab.dtype)
+    if lab.ndim != 1 or lab.shape[0] != sth.shape[0]:
+        raise ValueError("reward_probe: labels must be [N] with N = %d rows of states (got shape %s)" % (sth.shape[0], lab.shape))
+    if sth.shape[0] < 2:
+        raise ValueError("reward_probe: needs N >= 2 rows of states (N = %d)" % sth.shape[0])
+    if sth.shape[1] > REWARD_PROBE_MAX_S:
+        raise ValueError("reward_probe: the state dimension must lie in [1, %d] (S = %d)" % (REWARD_PROBE_MAX_S, sth.shape[1]))
+    if lab.min() < 0 or lab.max() > 1:
+        raise ValueError("reward_probe: labels must lie in {0, 1}, found [%d, %d]" % (int(lab.min()), int(lab.max())))
+    if not torch.cuda.is_available():
+        raise C.SrlzError("reward_probe runs on the GPU only (torch.cuda.is_available() is False): the srl-zoo_amd build has no "
+                          "CPU fallback")
+    device = torch.device("cuda", torch.cuda.current_device())
+    return RewardProbeData(torch.from_numpy(sth.astype(np.float32)).to(device),
+                           torch.from_numpy(np.ascontiguousarray(lab, dtype=np.int32)).to(device))
+
+
+def reward_probe_n_params(s):
+    """Linear(2S, 4), Linear(4, 4), Linear(4, 2) with their biases, flat in state_dict order."""
+    return 8 * int(s) + 34
+
+
+def reward_probe_chunk_rows(s):
+    """Rows of a minibatch that srlz_reward_probe_fit processes at a time (a function of S alone)."""
+    return C.reward_probe_chunk_rows(int(s))
+
+
+def reward_probe_stats(device=None):
+    """Zeroed statistics of one phase: (running_loss float64 [1], counts int64 [5] in the order of REWARD_PROBE_COUNTS)."""
+    device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+    return torch.zeros(1, dtype=torch.float64, device=device), torch.zeros(5, dtype=torch.int64, device=device)
+
+
+def _reward_probe_buffer(t, name, dtype, numel, data, exact=False):
+    if not torch.is_tensor(t) or t.device != data.states.device:
+        raise C.SrlzError("reward_probe: %s must be a tensor on %s: the srl-zoo_amd hot path has no CPU fallback" % (name, data.states.device))
+    if t.dtype != dtype:
+        raise ValueError("reward_probe: %s must be %s (got %s)" % (name, dtype, t.dtype))
+    if not t.is_contiguous():
+        raise ValueError("reward_probe: %s must be contiguous" % name)
+    if (t.numel() != numel) if exact else (t.numel() < numel):
+        raise ValueError("reward_probe: %s holds %d elements, needs %s%d (S = %d)" % (name, t.numel(), "" if exact else "at least ",
+                                                                                      numel, data.s))
+    return t
+
+
+def _reward_probe_table(data, idx):
+    """The minibatch table: int32 [n, B] on the HOST (the launcher checks every entry there), C-contiguous -> (host, device)."""
+    import numpy as np
+    if not isinstance(data, RewardProbeData):
+        raise ValueError("reward_probe: data must come from reward_probe_data()")
+    if isinstance(idx, np.ndarray):
+        idx = torch.from_numpy(idx)
+    if not torch.is_tensor(idx) or idx.device.type != "cpu":
+        raise ValueError("reward_probe: idx must be a host tensor (it is checked on the host, then uploaded)")
+    if idx.dtype != torch.int32:
+        raise ValueError("reward_probe: idx must be int32 (got %s)" % idx.dtype)
+    if idx.dim() != 2 or idx.shape[0] < 1 or idx.shape[1] < 1:
+        raise ValueError("reward_probe: idx must be a non-empty [minibatches, B] table (got shape %s)" % (tuple(idx.shape),))
+    if not idx.is_contiguous():
+        raise ValueError("reward_probe: idx must be contiguous")
+    return idx, idx.to(data.states.device)
+
+
+def reward_probe_fit(data, idx, params, m, v, t0, lr, running_loss, counts, step_loss=None, betas=(0.9, 0.999), eps=1e-8):
+    """idx.shape[0] consecutive Adam steps of the reward probe (Linear(2S,4)-ReLU-Linear(4,4)-ReLU-Linear(4,2), cross-entropy) in
+    ONE launch of srlz_reward_probe_fit: minibatch s is the rows [states[i] ; states[i + 1]] for i in idx[s].  No autograd: the
+    kernel owns the backward.  params / m / v: float32 [8S + 34] on the device in state_dict order, updated in place; t0: the Adam
+    steps already taken; running_loss float64 [1] and counts int64 [5] are added to (reward_probe_stats); step_loss: float64
+    [>= steps] for the mean loss of every step, or None."""
+    idx_h, idx_d = _reward_probe_table(data, idx)
+    n_steps, b = int(idx_h.shape[0]), int(idx_h.shape[1])
+    n_par = reward_probe_n_params(data.s)
+    for t, name in ((params, "params"), (m, "m"), (v, "v")):
+        _reward_probe_buffer(t, name, torch.float32, n_par, data, exact=True)
+    _reward_probe_buffer(running_loss, "running_loss", torch.float64, 1, data)
+    _reward_probe_buffer(counts, "counts", torch.int64, 5, data)
+    if step_loss is not None:
+        _reward_probe_buffer(step_loss, "step_loss", torch.float64, n_steps, data)
+    C.reward_probe_fit(ptr(data.states), ptr(data.labels), data.n, data.s, ptr(idx_d), ctypes.c_void_p(idx_h.data_ptr()), n_steps, b,
+                       ptr(params), ptr(m), ptr(v), int(t0), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                       ptr(running_loss), ptr(counts), ptr(step_loss), stream())
+
+
+def reward_probe_eval(data, idx, params, running_loss, counts):
+    """The forward, loss (float64 per row) and counts of idx.shape[0] minibatches in ONE launch of srlz_reward_probe_eval; params
+    are only read, running_loss and counts are added to."""
+    idx_h, idx_d = _reward_probe_table(data, idx)
+    n_batches, b = int(idx_h.shape[0]), int(idx_h.shape[1])
+    _reward_probe_buffer(params, "params", torch.float32, reward_probe_n_params(data.s), data, exact=True)
+    _reward_probe_buffer(running_loss, "running_loss", torch.float64, 1, data)
+    _reward_probe_buffer(counts, "counts", torch.int64, 5, data)
+    device = data.states.device
+    ticket = _REWARD_PROBE_TICKET.get(device.index)
+    if ticket is None:
+        ticket = _REWARD_PROBE_TICKET[device.index] = torch.zeros(1, dtype=torch.int32, device=device)
+    nbytes = C.reward_probe_eval_workspace(n_batches, b)
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=device)
+    C.reward_probe_eval(ptr(data.states), ptr(data.labels), data.n, data.s, ptr(idx_d), ctypes.c_void_p(idx_h.data_ptr()), n_batches, b,
+                        ptr(params), ptr(running_loss), ptr(counts), ptr(ws), nbytes, ptr(ticket), stream())
+
+
 def normalize_u8(frames, out=None):
     """uint8 [N,H,W,C] device tensor -> normalised fp32 [N,C,W,H] (the reference's observation tensor); `out`: where to
     write it (a contiguous [N,C,W,H] fp32 tensor, e.g. one half of a pair buffer)."""

@@ -494,8 +494,186 @@ def loop_child(name, path):
     np.savez_compressed(path, **loop_case(th, **LOOP_CASES[name]))
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# (9) evaluation/predict_reward.py, run as the script it is (it has no functions): runpy.run_path on the UNMODIFIED file, after
+# th.manual_seed(preseed) (its model is built before it seeds anything).  A trace function reads the script's own variables where it
+# prints them, so the losses are recorded at full precision next to the four decimals parsed from its output.
+# ---------------------------------------------------------------------------------------------------------------------------------
+REWARD_SCRIPT = os.path.join(REF, "evaluation", "predict_reward.py")
+REWARD_LINE_MODEL_BUILT, REWARD_LINE_STEP, REWARD_LINE_PRINT = 66, 122, 149  # criterion = ...; optimizer.zero_grad(); print(loss)
+
+
+def reward_probe_run(th, case):
+    import contextlib
+    import io
+    import re
+    import runpy
+    import tempfile
+    import dataset_util
+    import reward_util as ru
+    seen = {"init": None, "phases": [], "steps": 0}
+
+    def local_trace(frame, event, arg):
+        if event == "line":
+            g = frame.f_globals
+            if frame.f_lineno == REWARD_LINE_MODEL_BUILT and seen["init"] is None:
+                seen["init"] = {k: v.detach().clone() for k, v in g["model"].state_dict().items()}
+            elif frame.f_lineno == REWARD_LINE_STEP:
+                seen["steps"] += 1
+            elif frame.f_lineno == REWARD_LINE_PRINT and (g["epoch"], g["phase"]) != seen.get("last"):  # a two-line statement
+                seen["last"] = (g["epoch"], g["phase"])
+                seen["phases"].append(dict(epoch=g["epoch"], phase=g["phase"], loss=float(g["epoch_loss"]), acc=float(g["epoch_acc"]),
+                                           per_class=[float(g["corrects"][0]), float(g["corrects"][1])],
+                                           counts=[int(g["running_corrects"]), -1, -1, int(g["n_per_class"][0]),
+                                                   int(g["n_per_class"][1])],
+                                           running_loss=float(g["running_loss"]), n_batches=seen["steps"]))
+                seen["steps"] = 0
+        return local_trace
+
+    def global_trace(frame, event, arg):
+        return local_trace if frame.f_code.co_filename == REWARD_SCRIPT else None
+
+    with tempfile.TemporaryDirectory() as root:
+        # the arrays of tests/dataset_util.make_dataset, rewards rewritten as int64 (the script hands them to CrossEntropyLoss)
+        arrays = ru.case_arrays(case)
+        _, _, actions, rewards, starts = dataset_util.make_dataset(os.path.join(root, "check"), n_episodes=case["n_episodes"],
+                                                                   ep_len=case["ep_len"], seed=case["data_seed"])
+        assert np.array_equal(actions, arrays["actions"]) and np.array_equal(rewards, arrays["rewards"]) and \
+            np.array_equal(starts, arrays["episode_starts"])
+        with np.load(os.path.join(root, "check", "data", "tiny_test", "ground_truth.npz")) as gt:
+            assert np.array_equal(gt["ground_truth_states"], arrays["ground_truth_states"])
+            assert np.array_equal(gt["target_positions"], arrays["target_positions"])
+        argv = ru.write_case(root, case, int_rewards=True)
+        old_cwd, old_argv = os.getcwd(), list(sys.argv)
+        os.chdir(root)
+        out = io.StringIO()
+        try:
+            sys.argv = ["predict_reward.py"] + argv + ["--no-cuda"]
+            th.manual_seed(case["preseed"])
+            sys.settrace(global_trace)
+            with contextlib.redirect_stdout(out):
+                g = runpy.run_path(REWARD_SCRIPT, run_name="__main__")
+        finally:
+            sys.settrace(None)
+            os.chdir(old_cwd)
+            sys.argv = old_argv
+    text = out.getvalue()
+    epochs, bs = case["epochs"], case["bs"]
+    assert seen["init"] is not None and len(seen["phases"]) == 2 * epochs, (seen["init"] is None, len(seen["phases"]))
+    printed = re.findall(r"^(train|val) Loss: (\S+) Acc: (\S+)\nAccuracy per class: (\S+) (\S+)$", text, re.M)
+    assert len(printed) == 2 * epochs, text
+    best = re.search(r"^Best val Acc: (\S+)$", text, re.M)
+    rec = {}
+    for k in ru.KEYS:
+        rec["init/" + k] = seen["init"][k].numpy()
+        rec["final/" + k] = g["model"].state_dict()[k].detach().numpy()
+    final = [g["model"].state_dict()[k].detach().double() for k in ru.KEYS]
+    rec["final/names"] = np.array(ru.KEYS)
+    rec["final/sums"] = np.array([float(t.sum()) for t in final])
+    rec["final/abss"] = np.array([float(t.abs().sum()) for t in final])
+    # the trained model's logits on the first validation minibatch
+    idx = g["X_val"][:bs]
+    st = g["states"]
+    with th.no_grad():
+        logits = g["model"].rewardModel(th.Tensor(st[idx, :]).float(), th.Tensor(st[idx + 1, :]).float())
+    rec["eval_states/idx"] = idx.numpy()
+    rec["eval_states/full"] = logits.double().numpy()
+    shape = (epochs, 2)
+    rec["loss"] = np.array([p["loss"] for p in seen["phases"]]).reshape(shape)
+    rec["acc"] = np.array([p["acc"] for p in seen["phases"]]).reshape(shape)
+    rec["acc_per_class"] = np.array([p["per_class"] for p in seen["phases"]]).reshape(shape + (2,))
+    rec["counts"] = np.array([p["counts"] for p in seen["phases"]], dtype=np.int64).reshape(shape + (5,))
+    for c in (0, 1):  # correct per class = accuracy per class * rows of the class (nan where the class is empty -> 0 rows)
+        rec["counts"][..., 1 + c] = np.rint(np.nan_to_num(rec["acc_per_class"][..., c]) * rec["counts"][..., 3 + c])
+    rec["running_loss"] = np.array([p["running_loss"] for p in seen["phases"]]).reshape(shape)
+    rec["n_batches"] = np.array([p["n_batches"] for p in seen["phases"]], dtype=np.int64).reshape(shape)
+    assert [p["phase"] for p in seen["phases"]] == ["train", "val"] * epochs
+    rec["printed/loss"] = np.array([float(p[1]) for p in printed]).reshape(shape)
+    rec["printed/acc"] = np.array([float(p[2]) for p in printed]).reshape(shape)
+    rec["printed/acc_per_class"] = np.array([[float(p[3]), float(p[4])] for p in printed]).reshape(shape + (2,))
+    rec["best_val_acc"] = np.array(float(g["best_acc"]))
+    rec["printed/best_val_acc"] = np.array(float(best.group(1)))
+    rec["phase_sizes"] = np.array([len(g["X_train"]), len(g["X_val"])], dtype=np.int64)
+    rec["indices"] = g["indices"]
+    assert (rec["counts"][..., 1] + rec["counts"][..., 2] == rec["counts"][..., 0]).all()
+    assert np.abs(rec["printed/loss"] - rec["loss"]).max() <= 0.5001e-4
+    return rec
+
+
+def reward_probe_spread(th, case, rec):
+    """The reference's float32 run against the float64 restatement (tests/reward_util.py) over the same minibatch order from the same
+    initial parameters: its own float32-to-float64 spread, measured on the CPU."""
+    import golden_util
+    import reward_util as ru
+    flat = ru.flatten_state_dict({k: rec["init/" + k] for k in ru.KEYS})
+    states = np.asarray(ru.case_states(case), dtype=np.float32)  # the script feeds float32 rows
+    labels = np.maximum(ru.case_arrays(case)["rewards"], 0).astype(np.int64)
+    tables = ru.replay_tables(rec["indices"], case["seed"], case["bs"], case["epochs"])
+    m, v, t = np.zeros_like(flat), np.zeros_like(flat), 0
+    loss = np.zeros((case["epochs"], 2))
+    for e, (train, val) in enumerate(tables):
+        assert (len(train), len(val)) == tuple(rec["n_batches"][e]), (e, len(train), len(val), rec["n_batches"][e])
+        flat, m, v, ph, _ = ru.fit(flat, m, v, t, states, labels, train, case["lr"])
+        t += len(train)
+        loss[e, 0] = ph.running_loss / rec["phase_sizes"][0]
+        loss[e, 1] = ru.evaluate(flat, states, labels, val).running_loss / rec["phase_sizes"][1]
+    S = states.shape[1]
+    sd = {k: th.from_numpy(np.ascontiguousarray(a)) for k, a in zip(ru.KEYS, ru.unflatten(flat, S))}
+    logits = ru.forward(flat, ru.rows(states, rec["eval_states/idx"]))[2]
+    g = {k: rec[k] for k in ("final/names", "final/sums", "final/abss", "eval_states/full")}
+    worst, _ = golden_util.endpoint_errors(sd, g, case["lr"], t, logits)
+    return {"param": worst["param"], "eval_states": worst["eval_states"],
+            "loss": float((np.abs(rec["loss"] - loss) / np.abs(loss)).max()), "loss_first_last": [float(rec["loss"][0, 0]),
+                                                                                                  float(rec["loss"][-1, 0])]}
+
+
+def reward_probe_child(path):
+    _stub_modules()
+    sys.path.insert(0, REF)
+    import torch as th
+    th.set_num_threads(1)
+    import reward_util as ru
+    out, spread = {}, {}
+    for case in ru.CASES:
+        rec = reward_probe_run(th, case)
+        spread[case["name"]] = reward_probe_spread(th, case, rec)
+        print(case["name"], json.dumps(spread[case["name"]]), "train loss", rec["loss"][:, 0].round(4).tolist())
+        assert max(spread[case["name"]][k] for k in ("param", "eval_states", "loss")) <= 1e-3, "shorten the case: the spread exceeds 1e-3"
+        for k, a in rec.items():
+            out["%s/%s" % (case["name"], k)] = a
+    out["cases"] = np.array(json.dumps(list(ru.CASES)))
+    out["torch_version"] = np.array(th.__version__)
+    np.savez_compressed(path, **out)
+    with open(os.path.join(OUT, "reward_probe_spread.json"), "w") as f:
+        json.dump({"cases": spread, "refused_above": 1e-3,
+                   "metric": "the unmodified evaluation/predict_reward.py in float32 on the CPU against the float64 restatement of "
+                             "tests/reward_util.py, same initial parameters, same minibatch order: param = worst tensor of "
+                             "tests/golden_util.py::endpoint_errors (|sum - ref| and |abs-sum - ref| over abs-sum + lr * steps * "
+                             "numel), eval_states = its measure on the trained model's logits of the first validation minibatch, "
+                             "loss = max relative error of the per-epoch train and val losses"}, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
+def run_reward_probe_child():
+    import subprocess
+    import tempfile
+    tmp = tempfile.mktemp(suffix=".npz")
+    subprocess.check_call([sys.executable, os.path.abspath(__file__), "--reward-probe-child", tmp], timeout=1500)
+    with np.load(tmp, allow_pickle=False) as z:
+        d = {k: z[k] for k in z.files}
+    os.remove(tmp)
+    return d
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
+    only = [a for a in sys.argv[1:] if not a.startswith("-")]
+    if only and all(o.startswith("reward_probe") for o in only):  # a child process does all of it: nothing to import here
+        d = run_reward_probe_child()
+        path = os.path.join(OUT, "reward_probe.npz")
+        np.savez_compressed(path, **d)
+        print("wrote %-28s %6.1f KB  (%d arrays)" % ("reward_probe.npz", os.path.getsize(path) / 1024.0, len(d)))
+        return
     th, ref_pre, SRLModules, RL = import_reference()
 
     only = [a for a in sys.argv[1:] if not a.startswith("-")]
@@ -594,10 +772,14 @@ def main():
                                                 B=4, n_steps=4, lr=1e-4, val_steps=(2,)))
     for lname in LOOP_CASES:
         save(lname, lambda: run_loop_child(lname))
+    # (9) evaluation/predict_reward.py as a script (also writes reward_probe_spread.json)
+    save("reward_probe", run_reward_probe_child)
 
 
 if __name__ == "__main__":
     if len(sys.argv) == 4 and sys.argv[1] == "--loop-child":
         loop_child(sys.argv[2], sys.argv[3])
+    elif len(sys.argv) == 3 and sys.argv[1] == "--reward-probe-child":
+        reward_probe_child(sys.argv[2])
     else:
         main()
