@@ -798,6 +798,18 @@ int srlz_pca_transform(const uint8_t* x_u8, const float* x_f32, const float* nor
 /* Host-only: dump the virtual-grid program of a 64->64 convolution (tests interpret it on the CPU).
  * out: N,PH,PW,ss,Hs,Ws,ds,Hd,Wd,min_off,span,s2, then 9 x {src class, dst class, flat offset, weight tap}. */
 int srlz_conv64_debug_program(const srlz_conv64_desc* d, int backward_data, int* out, int cap);
+/* Host-only, launches nothing: the route an nn.Linear entry point would take (csrc/linear.hip decides it in one function, which the
+ * entry points execute and this call reports).  op: 0 = srlz_linear_fwd / _fwd_res, 1 = srlz_linear_bwd_data / _bwd_data_res (Kout = K
+ * for the plain one; the other ops ignore Kout), 2 = srlz_linear_bwd_weight.  a, b: the two operand ADDRESSES in the entry point's own
+ * order ((x, w), (dy, w), (dy, x)); only their alignment is looked at, they are not dereferenced.  has_ws / ws_bytes: whether the call
+ * would pass a workspace, and its size.
+ * out[0] = kernel: 0 gemm_strided_kernel, 1 gemm_vec_kernel<0,0>, 2 gemm_vec_kernel<0,1>, 3 gemm_vec_kernel<1,1>;
+ * out[1] = nz, the number of reduction chunks (1: the result is written directly and the workspace is not touched; > 1: the first
+ *          nz * I * J floats of the workspace hold the partial results, I x J the shape of the result);
+ * out[2] = rchunk, the length of a chunk (the whole reduction when nz = 1).
+ * SRLZ_ERR_BAD_DESC for an unknown op, an empty GEMM, or Kout outside [1, K] with op 1. */
+int srlz_linear_debug_route(int op, int M, int N, int K, int Kout, const void* a, const void* b, int has_ws, size_t ws_bytes,
+                            int out[3]);
 /* Back-to-back fp32 MFMA on random operands (no memory traffic): the matrix rate the chip sustains under load. */
 int srlz_debug_mfma_peak(float* out, int blocks, int iters, srlz_stream_t stream);
 /* The same MFMA stream with valu_per_mfma (0, 1, 2, 4, 8, 16) independent instructions of `kind` (0 v_fma_f32, 1 v_add_u32,

@@ -282,37 +282,68 @@ static bool vec_ok(const float* P, long long s_row, long long s_r, int nrow, int
   return false;
 }
 
-static int launch(const float* A, long long sai, long long sar, const float* B, long long sbr, long long sbj,
-                  const float* bias, float* C, int I, int J, int R, int relu, void* ws, size_t ws_bytes, hipStream_t st,
-                  const float* res = nullptr, long long ldr = 0) {
-  SRLZ_REQUIRE(I > 0 && J > 0 && R > 0, SRLZ_ERR_BAD_DESC, "linear: empty GEMM %dx%dx%d", I, J, R);
+// One GEMM as an entry point states it (the three directions of the header comment).
+struct Gemm {
+  const float *A, *B;
+  long long sai, sar, sbr, sbj;
+  int I, J, R;
+};
+static Gemm gemm_fwd(const float* x, const float* w, int M, int N, int K) { return {x, w, K, 1, 1, K, M, N, K}; }
+// (the first Kout of the K input columns: J = Kout columns of the K-wide w)
+static Gemm gemm_bwd_data(const float* dy, const float* w, int M, int N, int K, int Kout) { return {dy, w, N, 1, K, 1, M, Kout, N}; }
+static Gemm gemm_bwd_weight(const float* dy, const float* x, int M, int N, int K) { return {dy, x, 1, N, K, 1, N, K, M}; }
+
+// The route of one GEMM: which kernel, how many reduction chunks (nz = 1: the kernel writes the result itself, the workspace is not
+// touched; nz > 1: nz raw partial tiles in the workspace + splitk_combine_kernel) and their length.  The ONE place where this is
+// decided: launch() executes a plan, srlz_linear_debug_route reports it.
+enum { ROUTE_STRIDED = 0, ROUTE_VEC_RR = 1, ROUTE_VEC_RJ = 2, ROUTE_VEC_IJ = 3 };  // vec<AI,BI>: <0,0>, <0,1>, <1,1>
+struct Plan {
+  int kernel, nz, rchunk;
+  long long lda, ldb;
+};
+
+static int make_plan(const Gemm& g, bool has_ws, size_t ws_bytes, Plan* p) {
+  SRLZ_REQUIRE(g.I > 0 && g.J > 0 && g.R > 0, SRLZ_ERR_BAD_DESC, "linear: empty GEMM %dx%dx%d", g.I, g.J, g.R);
   bool ai = false, bi = false;
-  long long lda = 0, ldb = 0;
-  const bool vec = vec_ok(A, sai, sar, I, R, &ai, &lda) && vec_ok(B, sbj, sbr, J, R, &bi, &ldb);
+  p->lda = p->ldb = 0;
+  bool vec = vec_ok(g.A, g.sai, g.sar, g.I, g.R, &ai, &p->lda) && vec_ok(g.B, g.sbj, g.sbr, g.J, g.R, &bi, &p->ldb);
+  // A contiguous along i next to B contiguous along r: no entry point states such a GEMM (A runs along i only in the weight gradient,
+  // whose B = x runs along j or is not vectorisable — tests/test_linear_routes_cpu.py replays the predicate), so gemm_vec_kernel<1,0>
+  // is not instantiated; the strided kernel takes any operands.
+  if (ai && !bi) vec = false;
+  p->kernel = !vec ? ROUTE_STRIDED : ai ? ROUTE_VEC_IJ : bi ? ROUTE_VEC_RJ : ROUTE_VEC_RR;
   const int step = vec ? TR : BR;
-  int splits = ws ? choose_splits(I, J, R, ws_bytes, vec) : 1;
-  int rchunk = R, nz = 1;
+  const int splits = has_ws ? choose_splits(g.I, g.J, g.R, ws_bytes, vec) : 1;
+  p->rchunk = g.R;
+  p->nz = 1;
   if (splits > 1) {
-    rchunk = (R + splits - 1) / splits;
+    int rchunk = (g.R + splits - 1) / splits;
     rchunk = (rchunk + step - 1) / step * step;
-    nz = (R + rchunk - 1) / rchunk;
+    p->rchunk = rchunk;
+    p->nz = (g.R + rchunk - 1) / rchunk;
   }
+  return 0;
+}
+
+static int launch(const Gemm& g, const float* bias, float* C, int relu, void* ws, size_t ws_bytes, hipStream_t st,
+                  const float* res = nullptr, long long ldr = 0) {
+  Plan p;
+  if (int rc = make_plan(g, ws != nullptr, ws_bytes, &p)) return rc;
+  const int I = g.I, J = g.J, R = g.R, nz = p.nz, rchunk = p.rchunk;
   const dim3 grid((J + 63) / 64, (I + 63) / 64, nz);
   const float* kbias = nz > 1 ? nullptr : bias;
   float* kC = nz > 1 ? (float*)ws : C;
   const int krelu = nz > 1 ? 0 : relu;
   const float* kres = nz > 1 ? nullptr : res;
-  if (vec) {
 #define SRLZ_VEC_LAUNCH(AIV, BIV) \
-    SRLZ_LAUNCH((gemm_vec_kernel<AIV, BIV>), grid, dim3(256), 0, st, A, lda, B, ldb, kbias, kC, I, J, R, krelu, rchunk, kres, ldr)
-    if (ai && bi) SRLZ_VEC_LAUNCH(true, true);
-    else if (ai) SRLZ_VEC_LAUNCH(true, false);
-    else if (bi) SRLZ_VEC_LAUNCH(false, true);
-    else SRLZ_VEC_LAUNCH(false, false);
+  SRLZ_LAUNCH((gemm_vec_kernel<AIV, BIV>), grid, dim3(256), 0, st, g.A, p.lda, g.B, p.ldb, kbias, kC, I, J, R, krelu, rchunk, kres, ldr)
+  if (p.kernel == ROUTE_VEC_IJ) SRLZ_VEC_LAUNCH(true, true);
+  else if (p.kernel == ROUTE_VEC_RJ) SRLZ_VEC_LAUNCH(false, true);
+  else if (p.kernel == ROUTE_VEC_RR) SRLZ_VEC_LAUNCH(false, false);
+  else
+    SRLZ_LAUNCH(gemm_strided_kernel, grid, dim3(256), 0, st, g.A, g.sai, g.sar, g.B, g.sbr, g.sbj, kbias, kC, I, J, R, krelu, rchunk, kres,
+                ldr);
 #undef SRLZ_VEC_LAUNCH
-  } else {
-    SRLZ_LAUNCH(gemm_strided_kernel, grid, dim3(256), 0, st, A, sai, sar, B, sbr, sbj, kbias, kC, I, J, R, krelu, rchunk, kres, ldr);
-  }
   if (nz > 1) {
     SRLZ_LAUNCH(splitk_combine_kernel, dim3((I * J + 255) / 256), dim3(256), 0, st, (const float*)ws, nz, bias, C, I, J, relu, res, ldr);
   }
@@ -329,16 +360,31 @@ extern "C" size_t srlz_linear_workspace(int M, int N, int K) {
   return 16 * m * sizeof(float);
 }
 
+extern "C" int srlz_linear_debug_route(int op, int M, int N, int K, int Kout, const void* a, const void* b, int has_ws,
+                                       size_t ws_bytes, int out[3]) {
+  SRLZ_REQUIRE(out, SRLZ_ERR_NULL, "linear_debug_route: null pointer");
+  SRLZ_REQUIRE(op >= 0 && op <= 2, SRLZ_ERR_BAD_DESC, "linear_debug_route: unknown op %d", op);
+  SRLZ_REQUIRE(op != 1 || (Kout >= 1 && Kout <= K), SRLZ_ERR_BAD_DESC, "linear_debug_route: %d of %d input columns", Kout, K);
+  const float *fa = (const float*)a, *fb = (const float*)b;  // (looked at, never dereferenced)
+  const Gemm g = op == 0 ? gemm_fwd(fa, fb, M, N, K) : op == 1 ? gemm_bwd_data(fa, fb, M, N, K, Kout) : gemm_bwd_weight(fa, fb, M, N, K);
+  Plan p;
+  if (int rc = make_plan(g, has_ws != 0, ws_bytes, &p)) return rc;
+  out[0] = p.kernel;
+  out[1] = p.nz;
+  out[2] = p.rchunk;
+  return 0;
+}
+
 extern "C" int srlz_linear_fwd(const float* x, const float* w, const float* b, float* y, int M, int N, int K, int relu,
                                void* ws, size_t ws_bytes, srlz_stream_t stream) {
   SRLZ_REQUIRE(x && w && y, SRLZ_ERR_NULL, "linear_fwd: null pointer");
-  return launch(x, K, 1, w, 1, K, b, y, M, N, K, relu, ws, ws_bytes, as_stream(stream));
+  return launch(gemm_fwd(x, w, M, N, K), b, y, relu, ws, ws_bytes, as_stream(stream));
 }
 
 extern "C" int srlz_linear_fwd_res(const float* x, const float* w, const float* b, const float* res, float* y, int M, int N, int K,
                                    int relu, void* ws, size_t ws_bytes, srlz_stream_t stream) {
   SRLZ_REQUIRE(x && w && y && res, SRLZ_ERR_NULL, "linear_fwd_res: null pointer");
-  return launch(x, K, 1, w, 1, K, b, y, M, N, K, relu, ws, ws_bytes, as_stream(stream), res, N);
+  return launch(gemm_fwd(x, w, M, N, K), b, y, relu, ws, ws_bytes, as_stream(stream), res, N);
 }
 
 extern "C" int srlz_linear_bwd_data_res(const float* dy, const float* w, const float* res, float* dx, int M, int N, int K, int Kout,
@@ -346,19 +392,19 @@ extern "C" int srlz_linear_bwd_data_res(const float* dy, const float* w, const f
   SRLZ_REQUIRE(dy && w && dx && res, SRLZ_ERR_NULL, "linear_bwd_data_res: null pointer");
   SRLZ_REQUIRE(Kout >= 1 && Kout <= K, SRLZ_ERR_BAD_DESC, "linear_bwd_data_res: %d of %d input columns", Kout, K);
   // the first Kout columns of dy . W, plus the residual branch's gradient (res: [M, Kout])
-  return launch(dy, N, 1, w, K, 1, nullptr, dx, M, Kout, N, 0, ws, ws_bytes, as_stream(stream), res, Kout);
+  return launch(gemm_bwd_data(dy, w, M, N, K, Kout), nullptr, dx, 0, ws, ws_bytes, as_stream(stream), res, Kout);
 }
 
 extern "C" int srlz_linear_bwd_data(const float* dy, const float* w, float* dx, int M, int N, int K, void* ws,
                                     size_t ws_bytes, srlz_stream_t stream) {
   SRLZ_REQUIRE(dy && w && dx, SRLZ_ERR_NULL, "linear_bwd_data: null pointer");
-  return launch(dy, N, 1, w, K, 1, nullptr, dx, M, K, N, 0, ws, ws_bytes, as_stream(stream));
+  return launch(gemm_bwd_data(dy, w, M, N, K, K), nullptr, dx, 0, ws, ws_bytes, as_stream(stream));
 }
 
 extern "C" int srlz_linear_bwd_weight(const float* dy, const float* x, float* dw, float* db, int M, int N, int K,
                                       void* ws, size_t ws_bytes, srlz_stream_t stream) {
   SRLZ_REQUIRE(dy && x && dw, SRLZ_ERR_NULL, "linear_bwd_weight: null pointer");
-  if (int rc = launch(dy, 1, N, x, K, 1, nullptr, dw, N, K, M, 0, ws, ws_bytes, as_stream(stream))) return rc;
+  if (int rc = launch(gemm_bwd_weight(dy, x, M, N, K), nullptr, dw, 0, ws, ws_bytes, as_stream(stream))) return rc;
   if (db) {
     SRLZ_LAUNCH(colsum_kernel, dim3((N + 63) / 64), dim3(256), 0, as_stream(stream), dy, db, M, N);
   }

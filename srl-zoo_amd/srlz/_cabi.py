@@ -88,6 +88,7 @@ _PROTOS = {
     "srlz_conv64_wino_bwd_data_pool_sums": (c_int, [P, P, P, P, P, P, P, _PD, P, _C64, P]),
     "srlz_conv64_bwd_weight": (c_int, [P, P, P, P, P, _BO, P, c_size_t, _C64, P]),
     "srlz_conv64_debug_program": (c_int, [_C64, c_int, POINTER(c_int), c_int]),
+    "srlz_linear_debug_route": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_size_t, POINTER(c_int)]),
     "srlz_debug_placement": (c_int, [P, c_int, c_int, c_int, P]),
     "srlz_debug_mfma_peak": (c_int, [P, c_int, c_int, P]),
     "srlz_debug_mfma_valu": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P]),
