@@ -755,6 +755,28 @@ int srlz_reward_probe_eval(const float* states /*[N,S]*/, const int* labels /*[N
                            long long* counts /*[5]*/, void* ws, size_t ws_bytes, unsigned* ticket, srlz_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Evaluation: decoded tensors into pictures (csrc/latent.hip).  Replaces, per shown image,
+ *   img = detachToNumpy(net_out)[0].T; img = deNormalize(img, mode="image_net"); return img[:, :, ::-1]
+ *                                                                                         evaluation/enjoy_latent.py:36-39
+ * with deNormalize = x[..., c] *= std[c]; x[..., c] += mean[c]; np.clip(x, 0, 1)           preprocessing/utils.py:54-66
+ * dec [N, 3, W, H] is the decoder's output in the reference's tensor layout (W-major planes).
+ *   srlz_decoded_to_bgr: img [N, H, W, 3] fp32 with img[i][y][x][2 - c] = clip(fadd(fmul(dec[i][c][x][y], std[c]), mean[c]), 0, 1),
+ *   std = (0.229, 0.224, 0.225) and mean = (0.485, 0.456, 0.406) as fp32.  The product and the sum are rounded separately (no fma):
+ *   the result has the bits of the numpy expression.  A NaN stays a NaN, as in np.clip.
+ *   srlz_decoded_to_sheet_u8: the same pictures as bytes, (uint8) rintf(fmul(v, 255)) with v the value above (round half to even:
+ *   np.rint(v * np.float32(255)).astype(np.uint8); a NaN gives 0), tiled into ONE sheet [sheet_h, sheet_w, 3]: picture i at tile
+ *   (i / cols, i % cols) of a grid of rows = ceil(n / cols) by cols tiles, `gap` pixels of `fill` between the tiles and around the
+ *   grid, the empty tiles of the last row `fill` too.  rgb != 0 keeps the channel order R, G, B, rgb == 0 writes B, G, R.  Every
+ *   byte of the sheet is written exactly once.  sheet_h = rows * h + (rows + 1) * gap and sheet_w = cols * w + (cols + 1) * gap.
+ * Both are transposes staged through LDS (reads and writes coalesced), any w and h.  n, w, h, cols >= 1, gap >= 0, 0 <= fill <= 255,
+ * n * 3 * w * h and the sheet's byte count below 2^31, sheet_h and sheet_w as above; anything else is SRLZ_ERR_BAD_DESC, a null
+ * pointer SRLZ_ERR_NULL — all before any launch.
+ * ------------------------------------------------------------------------------------------------------------ */
+int srlz_decoded_to_bgr(const float* dec /*[N,3,W,H]*/, int n, int w, int h, float* img /*[N,H,W,3]*/, srlz_stream_t stream);
+int srlz_decoded_to_sheet_u8(const float* dec /*[N,3,W,H]*/, int n, int w, int h, int cols, int gap, int fill, int rgb,
+                             unsigned char* sheet /*[sheet_h,sheet_w,3]*/, int sheet_h, int sheet_w, srlz_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * PCA baseline: sklearn's IncrementalPCA in fp64 through a Gram matrix (csrc/pca.hip).  Replaces, per minibatch,
  *   ipca.partial_fit(toNumpyMatrix(obs_var))      srl_baselines/pca.py:107-108   (one LAPACK SVD of a (k + bs + 1) x D matrix)
  *   ipca.transform(toNumpyMatrix(obs_var))        srl_baselines/pca.py:117-118

@@ -201,6 +201,8 @@ _PROTOS = {
                                       P, P, P]),
     "srlz_reward_probe_eval_workspace": (c_size_t, [c_int, c_int]),
     "srlz_reward_probe_eval": (c_int, [P, P, c_int, c_int, P, P, c_int, c_int, P, P, P, P, c_size_t, P, P]),
+    "srlz_decoded_to_bgr": (c_int, [P, c_int, c_int, c_int, P, P]),
+    "srlz_decoded_to_sheet_u8": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P]),
     "srlz_pca_workspace": (c_size_t, [c_int, c_int]),
     "srlz_pca_transform_workspace": (c_size_t, [c_int, c_int, c_int]),
     "srlz_pca_stats": (c_int, [P, P, P, c_int, c_int, c_int, c_longlong, P, P, P, P, P]),

@@ -1891,6 +1891,51 @@ def gt_correlation(gt, states):
     return corr.cpu().numpy()
 
 
+def _check_decoded(dec, who):
+    """A decoded batch [N, 3, W, H] for csrc/latent.hip: float32 on the GPU, three channels — the assertion of the reference's
+    deNormalize (preprocessing/utils.py:49) as an SrlzError."""
+    if not torch.is_tensor(dec) or dec.dim() != 4:
+        raise C.SrlzError("%s: dec must be a [N, 3, W, H] tensor (got %s)" % (who, tuple(dec.shape) if torch.is_tensor(dec) else type(dec)))
+    dec = _check(dec, "%s: dec" % who)
+    if dec.shape[1] != 3:
+        raise C.SrlzError("%s: dec must have 3 channels, [N, 3, W, H] (got %s)" % (who, tuple(dec.shape)))
+    return dec
+
+
+def decoded_to_bgr(dec):
+    """Decoded images [N, 3, W, H] (the reference's tensor layout) -> the float32 [N, H, W, 3] BGR images of the reference's getImage
+    (evaluation/enjoy_latent.py:36-39): transposed, de-normalised with the image_net constants, clipped to [0, 1], channels flipped
+    — bit for bit the numpy expression (csrc/latent.hip)."""
+    dec = _check_decoded(dec, "decoded_to_bgr")
+    n, _, w, h = dec.shape
+    img = torch.empty((n, h, w, 3), dtype=torch.float32, device=dec.device)
+    C.decoded_to_bgr(ptr(dec), n, w, h, ptr(img), stream())
+    return img
+
+
+def sheet_size(n, w, h, cols, gap):
+    """(sheet_h, sheet_w) of n pictures of h x w in a grid of `cols` columns with `gap` pixels between the tiles and around the grid."""
+    rows = (n + cols - 1) // cols
+    return rows * h + (rows + 1) * gap, cols * w + (cols + 1) * gap
+
+
+def decoded_to_sheet(dec, cols, gap=2, fill=255, rgb=True):
+    """Decoded images [N, 3, W, H] -> ONE uint8 sheet [SH, SW, 3] on the device: picture i at tile (i // cols, i % cols), `gap` pixels
+    of `fill` between the tiles and around the grid, empty tiles `fill`.  Pixel values are np.rint(v * 255) of decoded_to_bgr's v;
+    rgb=True keeps R, G, B (what PIL wants), False writes B, G, R (csrc/latent.hip)."""
+    dec = _check_decoded(dec, "decoded_to_sheet")
+    n, _, w, h = dec.shape
+    cols, gap, fill = int(cols), int(gap), int(fill)
+    if cols < 1 or gap < 0 or not 0 <= fill <= 255:
+        raise C.SrlzError("decoded_to_sheet: needs cols >= 1, gap >= 0 and fill in [0, 255] (cols=%d, gap=%d, fill=%d)" % (cols, gap, fill))
+    sh, sw = sheet_size(n, w, h, cols, gap)
+    if sh * sw * 3 >= 2 ** 31:
+        raise C.SrlzError("decoded_to_sheet: the sheet of %d x %d pixels must stay below 2^31 bytes" % (sh, sw))
+    sheet = torch.empty((sh, sw, 3), dtype=torch.uint8, device=dec.device)
+    C.decoded_to_sheet_u8(ptr(dec), n, w, h, cols, gap, fill, 1 if rgb else 0, ptr(sheet), sh, sw, stream())
+    return sheet
+
+
 REWARD_PROBE_MAX_S = 512  # include/srlz.h, srlz_reward_probe_fit: the parameters and their Adam moments stay in LDS
 REWARD_PROBE_COUNTS = ("correct", "correct_0", "correct_1", "rows_0", "rows_1")  # the five int64 counters, in this order
 _REWARD_PROBE_TICKET = {}
