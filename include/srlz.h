@@ -815,6 +815,54 @@ int srlz_pca_transform(const uint8_t* x_u8, const float* x_f32, const float* nor
                        size_t ws_bytes, srlz_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Deployment encoder (csrc/infer.hip): camera frames to states in four launches.  Replaces, per call of
+ *   model.getStates(obs) in eval mode                                  models/models.py:25-30, 131-139; autoencoders.py:107-108
+ * the three encoder blocks  Conv2d, BatchNorm2d, ReLU, MaxPool2d(3, 2)  models/models.py:47-63
+ * each as ONE launch,  pooled = maxpool3x3s2(relu(conv(x) * scale + shift)),  scale / shift = the record srlz_bn_eval_params
+ * produces (floats [128,192) and [192,256)), applied with the arithmetic of srlz_bn_relu_pool_fwd.  The raw convolution output is
+ * never written.  The state head is the existing srlz_linear_fwd on the last block's [N,64,hp,wp] output.
+ *   kind SRLZ_INFER_IN    7x7 stride 2 pad 3, c_in in {3, 6} -> 64   models/models.py:49-52   x: uint8 frames through norm_lut
+ *   kind SRLZ_INFER_MID   3x3 stride 1 pad 1, 64 -> 64               models/models.py:54-57   x: fp32 NHWC
+ *   kind SRLZ_INFER_LAST  3x3 stride 2 pad 1, 64 -> 64               models/models.py:59-62   x: fp32 NHWC
+ * hi / wi are the two spatial sizes of the tensor the convolution sees (the reference's [B,C,D1,D2]: D1 = hi).  The byte input of
+ * kind IN is addressed by ELEMENT strides: element (n, c, y, x) is byte n*stride_n + c*stride_c + y*stride_y + x*stride_x, and
+ * channel c reads row c % 3 of the srlz_normalize_lut table (preprocessing/utils.py:20-32), as srlz_conv1_fwd_u8 does.  The reference's
+ * planar [N,C,W,H] tensor (strides C*hi*wi, hi*wi, wi, 1) and a camera's [N,H,W,C] frames (hi = W, wi = H; strides H*W*C, 1, C, W*C:
+ * the spatial swap of preprocessing/data_loader.py:255 as a stride choice) are the same kernel, no layout pass, identical bits.
+ * A 64-channel input is contiguous NHWC and its strides say so (hi*wi*64, 1, wi*64, 64).
+ * Output: pooled [N,hp,wp,64], or with out_nchw [N,64,hp,wp] (flat c*hp*wp + h*wp + w: what Linear(2304, S) reads), where
+ * hc = (hi + 2 pad - k) / stride + 1 and hp = (hc + 2 pool_pad - 3) / 2 + 1, the same for the widths.  Any map size, rectangular
+ * included.  No float atomics; every output's sum has one order that depends on neither n nor the tile boundaries: two runs are
+ * bit-identical and row i of a batch has the bits of that frame run alone.
+ * Rejected before any launch with SRLZ_ERR_BAD_DESC (srlz_infer_block_supported says so first): an unknown kind, c_in outside the
+ * table, a map whose convolution or pooled output would be empty, pool_pad / out_nchw outside {0, 1}, strides that make two elements
+ * share an address (kind IN) or that are not the contiguous NHWC ones (MID, LAST), more than 2^31 - 1 tiles.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define SRLZ_INFER_IN 0
+#define SRLZ_INFER_MID 1
+#define SRLZ_INFER_LAST 2
+typedef struct {
+  int n;          /* frames */
+  int c_in;       /* 3 or 6 (IN), 64 (MID, LAST) */
+  int hi, wi;     /* input map */
+  int kind;       /* SRLZ_INFER_* */
+  int pool_pad;   /* 0 or 1: models/models.py:52 (1), 57, 62 (0) */
+  int out_nchw;   /* 1: [N,64,hp,wp] (autoencoders.py:107-108: x.view(x.size(0), -1) of the NCHW map) */
+  long long stride_n, stride_c, stride_y, stride_x; /* input element strides */
+} srlz_infer_block_desc;
+int srlz_infer_block_supported(const srlz_infer_block_desc* d);
+/* Sizes of the convolution output (never stored) and of the pooled map; any of the four pointers may be NULL.  Host only. */
+int srlz_infer_block_out_dims(const srlz_infer_block_desc* d, int* hc, int* wc, int* hp, int* wp);
+/* Edge of the square tile of POOLED outputs one workgroup owns (host only; tests size their multi-tile cases by it). */
+int srlz_infer_tile(void);
+/* The kernels' private copy of a Conv2d weight [64, c_in, k, k] (nn.Conv2d, models/models.py:49, 54, 59): floats it takes (0 for a
+ * kind / c_in outside the table) and the packing launch. */
+long long srlz_infer_packed_floats(int kind, int c_in);
+int srlz_infer_pack_weights(const float* w_ref, float* wpack, int kind, int c_in, srlz_stream_t stream);
+int srlz_infer_block(const void* x, const float* norm_lut /* kind IN only */, const float* wpack, const float* bnp, float* out,
+                     const srlz_infer_block_desc* d, srlz_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Debug / calibration hooks (not on the product path).
  * ------------------------------------------------------------------------------------------------------------ */
 /* Host-only: dump the virtual-grid program of a 64->64 convolution (tests interpret it on the CPU).

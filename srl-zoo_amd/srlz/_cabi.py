@@ -53,12 +53,22 @@ class BnBwdOperand(Structure):
                 ("dy_out", c_void_p)]
 
 
+class InferBlockDesc(Structure):
+    """srlz_infer_block_desc; build with srlz.ops.infer_desc()."""
+    _fields_ = [("n", c_int), ("c_in", c_int), ("hi", c_int), ("wi", c_int), ("kind", c_int), ("pool_pad", c_int),
+                ("out_nchw", c_int), ("stride_n", c_longlong), ("stride_c", c_longlong), ("stride_y", c_longlong),
+                ("stride_x", c_longlong)]
+
+
+INFER_IN, INFER_MID, INFER_LAST = 0, 1, 2
+
 P = c_void_p
 _BO = POINTER(BnBwdOperand)
 _C64 = POINTER(Conv64Desc)
 _SK = POINTER(SkinnyDesc)
 _PD = POINTER(PoolDesc)
 _CN = POINTER(ConvNDesc)
+_IB = POINTER(InferBlockDesc)
 
 # name -> (restype, argtypes); restype c_int functions are status-checked
 _PROTOS = {
@@ -226,6 +236,12 @@ _PROTOS = {
     "srlz_comm_destroy": (c_int, []),
     "srlz_adam_step": (c_int, [P, P, P, P, c_longlong, c_double, c_double, c_double, c_double, c_int, c_float, P]),
     "srlz_adam_step_dev": (c_int, [P, P, P, P, c_longlong, c_double, c_double, c_double, c_double, P, P, c_float, P]),
+    "srlz_infer_block_supported": (c_int, [_IB]),
+    "srlz_infer_block_out_dims": (c_int, [_IB, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "srlz_infer_tile": (c_int, []),
+    "srlz_infer_packed_floats": (c_longlong, [c_int, c_int]),
+    "srlz_infer_pack_weights": (c_int, [P, P, c_int, c_int, P]),
+    "srlz_infer_block": (c_int, [P, P, P, P, P, _IB, P]),
 }
 
 # entry points whose int return value is data, not a status
@@ -235,7 +251,8 @@ _NOT_STATUS = {"srlz_version", "srlz_device_cus", "srlz_conv64_fwd_tiles", "srlz
                "srlz_conv64_bwd_data_tiles", "srlz_conv64_bwd_fused_bn_rows", "srlz_conv64_wino_supported", "srlz_conv64_wino_packed_floats",
                "srlz_conv64_wino_tiles", "srlz_conv64_wino_bwd_data_rows",
                "srlz_conv64_debug_program", "srlz_comm_world", "srlz_dense_supported",
-               "srlz_dense_out_fwd_loss_workgroups", "srlz_reward_probe_chunk_rows"}
+               "srlz_dense_out_fwd_loss_workgroups", "srlz_reward_probe_chunk_rows", "srlz_infer_block_supported",
+               "srlz_infer_tile"}
 
 EXPORTED = sorted(_PROTOS.keys())
 

@@ -2099,3 +2099,58 @@ def bn_replay_many(items):
         table[i].batch_stat, table[i].running_mean, table[i].running_var = st.data_ptr(), rm.data_ptr(), rv.data_ptr()
         table[i].num_batches_tracked = tick.data_ptr() if tick is not None else None
     C.bn_replay_many(table, len(items), BN_MOMENTUM, stream())
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# Deployment encoder (csrc/infer.hip): one eval-mode encoder block per launch, conv + BatchNorm + ReLU + MaxPool — models/models.py:47-63.
+# Thin: the caller (srlz/deploy.py) owns every buffer; nothing is allocated here, and no autograd node is made.
+# ----------------------------------------------------------------------------------------------------------------
+INFER_IN, INFER_MID, INFER_LAST = C.INFER_IN, C.INFER_MID, C.INFER_LAST
+INFER_POOL_PAD = {INFER_IN: 1, INFER_MID: 0, INFER_LAST: 0}  # models/models.py:52, 57, 62
+
+
+def infer_desc(kind, n, c_in, hi, wi, strides=None, pool_pad=None, out_nchw=None):
+    """srlz_infer_block_desc of `n` maps [c_in, hi, wi].  strides = element strides (n, c, y, x) of the input; None: the reference's
+    planar bytes for kind IN, contiguous NHWC for the 64-channel kinds.  pool_pad / out_nchw default to the reference's block of that
+    kind (the last block writes the NCHW-flat order the state head reads)."""
+    if strides is None:
+        strides = (c_in * hi * wi, hi * wi, wi, 1) if kind == INFER_IN else (hi * wi * 64, 1, wi * 64, 64)
+    if pool_pad is None:
+        pool_pad = INFER_POOL_PAD.get(kind, 0)
+    if out_nchw is None:
+        out_nchw = kind == INFER_LAST
+    return C.InferBlockDesc(n, c_in, hi, wi, kind, pool_pad, 1 if out_nchw else 0, *[int(s) for s in strides])
+
+
+def infer_supported(d):
+    return bool(C.infer_block_supported(ctypes.byref(d)))
+
+
+def infer_out_dims(d):
+    """(hc, wc, hp, wp): convolution output (never stored) and pooled map of a supported descriptor; SrlzError for a rejected one."""
+    v = [ctypes.c_int(0) for _ in range(4)]
+    C.infer_block_out_dims(ctypes.byref(d), *[ctypes.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def infer_pack(weight, kind, out=None):
+    """The kernels' copy of a Conv2d weight [64, c_in, k, k] (written into `out` when given: a refresh allocates nothing)."""
+    weight = _check(weight.detach(), "infer_pack weight")
+    c_in = weight.shape[1]
+    nfl = C.infer_packed_floats(kind, c_in)
+    k = 7 if kind == INFER_IN else 3
+    if nfl <= 0 or tuple(weight.shape) != (64, c_in, k, k):
+        raise C.SrlzError("infer_pack: no block of kind %d takes a weight of shape %s" % (kind, tuple(weight.shape)))
+    if out is None:
+        out = torch.empty(nfl, dtype=torch.float32, device=weight.device)
+    elif out.numel() != nfl or out.dtype != torch.float32 or not out.is_contiguous():
+        raise C.SrlzError("infer_pack: `out` must be %d contiguous float32 values" % nfl)
+    C.infer_pack_weights(ptr(weight), ptr(out), kind, c_in, stream())
+    return out
+
+
+def infer_block(x, wpack, bnp, out, d, lut=None):
+    """One launch: out = maxpool3x3s2(relu(conv(x) * scale + shift)) as `d` describes it.  x: uint8 frames (kind IN, with the
+    normalisation table) or fp32 NHWC; `out` must hold n * 64 * hp * wp floats."""
+    C.infer_block(ptr(x), ptr(lut), ptr(wpack), ptr(bnp), ptr(out), ctypes.byref(d), stream())
+    return out
