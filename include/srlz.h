@@ -130,6 +130,11 @@ int srlz_conv64_bwd_fused_supported(const srlz_conv64_desc* d);
  * /root/reference/models/models.py:59, and the first ConvTranspose's data gradient) — rather than conv64_fwd_kernel: what a profile
  * will list the launch under. */
 int srlz_conv64_gather_pipe_supported(const srlz_conv64_desc* d, int backward_data);
+/* != 0: srlz_conv64_fwd of this layer (backward_data = 0; a data gradient never does) — with or without bias, plain operand or x_bnp —
+ * runs as conv64_scatter_pipe_kernel, the software-pipelined persistent kernel of the stride-2 scatter programs (the forward of
+ * ConvTranspose2d(64, 64, 3, stride 2), reference models/models.py:66-78), rather than conv64_fwd_kernel.  y and stats_partial
+ * are bit-identical between the two.  Host only: no launch. */
+int srlz_conv64_scatter_pipe_supported(const srlz_conv64_desc* d, int backward_data);
 size_t srlz_conv64_bwd_fused_workspace(const srlz_conv64_desc* d);
 /* x_bn_bwd_partial (may be NULL; round 6): dx of this call is dA of the BatchNorm + ReLU that produced the layer's input from x —
  * the previous decoder block's (models/models.py:67-77) — and the tile that writes it holds relu(bn(x)) of the same positions, so the

@@ -529,7 +529,8 @@ static size_t fwd_lds_bytes(const ConvProg& P) {  // source rows, slab, row tabl
 }
 
 static int launch_fwd(const float* src, const float* wpack, const float* bias, float* dst, float* stats,
-                      const ConvProg& P, hipStream_t st, const OpFuse src_fuse = SRLZ_NO_FUSE, const PoolSum* psum = nullptr) {
+                      const ConvProg& P, hipStream_t st, const OpFuse src_fuse = SRLZ_NO_FUSE, const PoolSum* psum = nullptr,
+                      bool forward = false) {
   const int ntiles = P.G * P.tpg;
   const size_t lds = fwd_lds_bytes(P);
   SRLZ_REQUIRE(lds <= 160 * 1024, SRLZ_ERR_BAD_DESC, "conv64: tile needs %zu bytes of LDS", lds);
@@ -567,6 +568,9 @@ static int launch_fwd(const float* src, const float* wpack, const float* bias, f
     // plain stride-2 gather programs with many tiles (conv3 forward at training batch sizes): the software-pipelined persistent
     // kernel (gather_pipe_ok: a per-group criterion, so that one BatchNorm group alone and the batched pair take the same kernel)
     if (!src_fuse.bnp && !bias && conv64::gather_pipe_ok(P)) return conv64::launch_gather_pipe(src, wpack, dst, stats, P, st);
+    // a stride-2 ConvTranspose's forward with many tiles: the pipelined persistent kernel of the scatter programs, bit-identical to
+    // conv64_fwd_kernel<4, false> in y and in the statistics (scatter_pipe_ok: per group as well)
+    if (forward && conv64::scatter_pipe_ok(P)) return conv64::launch_scatter_pipe(src, wpack, bias, dst, stats, src_fuse.bnp, P, st);
     SRLZ_FWD_LAUNCH(4, false);
   }
 #undef SRLZ_FWD_LAUNCH
@@ -608,7 +612,8 @@ extern "C" int srlz_conv64_fwd(const float* x, const float* wpack_fwd, const flo
   ConvProg P;
   if (int rc = conv64::with_program(d, 0, &P)) return rc;
   SRLZ_REQUIRE(x && wpack_fwd && y, SRLZ_ERR_NULL, "conv64_fwd: null pointer");
-  return launch_fwd(x, wpack_fwd, bias, y, stats_partial, P, as_stream(stream), OpFuse{x_bnp, nullptr, nullptr, 0.f, 0, nullptr});
+  return launch_fwd(x, wpack_fwd, bias, y, stats_partial, P, as_stream(stream), OpFuse{x_bnp, nullptr, nullptr, 0.f, 0, nullptr}, nullptr,
+                    true);
 }
 
 extern "C" int srlz_conv64_bwd_data(const float* dy, const float* wpack_bwd, float* dx, const srlz_bn_bwd_operand* dy_bn,

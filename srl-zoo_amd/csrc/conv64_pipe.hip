@@ -1,4 +1,5 @@
-// conv64_pipe.hip — the software-pipelined persistent kernels of the 3x3, 64 -> 64 stride-2 gather programs (formulation: conv64.hip).
+// conv64_pipe.hip — the software-pipelined persistent kernels of the 3x3, 64 -> 64 stride-2 programs (formulation: conv64.hip): the gather
+// programs' two, described next, and the scatter programs' conv64_scatter_pipe_kernel (a ConvTranspose's forward), described at its place.
 //
 // ---------------------------------------------------------------------------------------------------------------
 // Software-pipelined, persistent kernels of the stride-2 gather programs (conv64_bwd_fused_kernel: the whole backward of a
@@ -822,6 +823,291 @@ __global__ __launch_bounds__(256) void conv64_bnpart_zero_scale_kernel(const flo
   bn_bwd_combine_store(s1, s2, bnpart + ((size_t)g * bn_rows + first_row + blockIdx.x) * 128);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The stride-2 SCATTER programs — the forward of a ConvTranspose2d(64, 64, 3, stride 2): one source class, four destination classes
+// with 4 / 2 / 2 / 1 taps — persistent and software-pipelined.  conv64_fwd_kernel<4, false> runs such a tile as: row table, rowinfo,
+// ONE synchronous staging of the 128 + span source rows (an HBM round trip between two barriers, with the fused relu(bn(.)) of the
+// previous block on the way in), nine taps through a run-time class switch (zeroing of 32 accumulator registers per class, a flush
+// with an exec branch around each 16-byte store).  Here
+//  * workgroups are persistent (2 per CU) and walk their XCD's run of tiles; the NEXT tile's row table is built under tap 6, its rows
+//    are requested into registers behind the barrier that opens tap 7 (branch-free: clamped addresses, masks applied at the landing)
+//    and land in LDS — through the same relu(bn(.)) expression, rows outside the tensor as zeros — behind the barrier that closes
+//    tap 8; tap 0's slab of the next tile travels under tap 8;
+//  * the tap structure is compile-time ({0..3}, {4, 5}, {6, 7}, {8}): no class switch, and the first MFMA of a class takes C = 0
+//    instead of 32 zeroed registers;
+//  * the flush is branch-free: a lane that must not write stores out of its buffer's range (GP_DROP).
+// The wave tile stays conv64_fwd_kernel's — 4 waves of 32 rows x 64 channels, NOT the 8 waves of 32 x 32 of the gather kernels above:
+// a tile's BatchNorm partial is one sequential chain per lane (channels 4 (lane & 15) .., rows (lane >> 4) + 4 k of each 16-row
+// half, class after class); a wave of 32 x 32 has only 32 such chains, so half its lanes would idle through twice as many flush
+// instructions per MFMA, or every flushed value would first have to move to the lane that owns its chain.  Same tiles, same MFMAs
+// in the same order, same flush layout, same summation order: y AND stats_partial are bit-identical to conv64_fwd_kernel<4, false>'s.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int SP_THREADS = 256;
+constexpr int SP_RP = SP_THREADS / 16;   // rows per pass
+constexpr int SP_BATCH = 12;             // rows (of 16 lanes) per thread: 128 + span <= 192
+constexpr int ST_WORDS = SP_RP * SP_BATCH;
+
+struct ScatterRows {
+  f32x4 v[SP_BATCH];
+  unsigned ok;  // bit j: row j lies inside the tensor
+};
+
+// The source-side row table of a scatter tile (cf. gtab_build): row R at (R & 15) * SP_BATCH + (R >> 4) — the twelve rows of thread t
+// (R = (t >> 4) + 16 j) are consecutive words.  The staged range begins at q0 + min_off < q0: built SHIFTED.
+__device__ __forceinline__ void stab_build(unsigned* __restrict__ tab, const ConvProg& P, int qstart, int nrows) {
+  int R = threadIdx.x;
+  asm volatile("" : "+v"(R));
+  if (R < ST_WORDS) {
+    unsigned e = 0;
+    if (R < nrows) e = src_entry<true>(P, qstart + R, P.ss);
+    tab[(R & (SP_RP - 1)) * SP_BATCH + (R >> 4)] = e;
+  }
+}
+
+__device__ __forceinline__ void scatter_request(ScatterRows& r, const float* __restrict__ src, const unsigned* __restrict__ tab) {
+  int t = threadIdx.x;
+  asm volatile("" : "+v"(t));
+  const int slot = t & 15;
+  const unsigned* __restrict__ tp = tab + (t >> 4) * SP_BATCH;
+  const uint4 e0 = *(const uint4*)tp, e1 = *(const uint4*)(tp + 4), e2 = *(const uint4*)(tp + 8);
+  const unsigned e[SP_BATCH] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w, e2.x, e2.y, e2.z, e2.w};
+  static_assert(SP_BATCH == 12, "the table read above takes twelve rows");
+  unsigned okmask = 0;
+#pragma unroll
+  for (int j = 0; j < SP_BATCH; ++j) {
+    // the one source class of a scatter program is class 0 (bit 0 of the entry); any row outside reads pixel 0 and lands as zeros
+    const unsigned m = (unsigned)__builtin_amdgcn_sbfe((int)e[j], 0u, 1u);
+    const unsigned off = (((e[j] >> 4) << 6) & m) + slot * 4;
+    r.v[j] = *(const f32x4*)(src + off);
+    okmask |= m & (1u << j);
+  }
+  r.ok = okmask;
+}
+
+// lrec (FUSE): scale, shift of the tile's BatchNorm group in LDS — relu(bn(raw)) as stage_rows_tab has it: hipcc contracts that one's
+// v * scale + shift into a fused multiply-add everywhere; written out here, because contraction is the compiler's choice per site
+template <bool FUSE>
+__device__ __forceinline__ void scatter_land(float* __restrict__ lds, ScatterRows& r, int nrows, const float* __restrict__ lrec) {
+  int t = threadIdx.x;
+  asm volatile("" : "+v"(t));
+  const int slot = t & 15;
+  f32x4 sc4 = {1.f, 1.f, 1.f, 1.f}, sh4 = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (FUSE) { sc4 = *(const f32x4*)(lrec + slot * 4); sh4 = *(const f32x4*)(lrec + 64 + slot * 4); }
+#pragma unroll
+  for (int j = 0; j < SP_BATCH; ++j) {
+    const int R = (t >> 4) + SP_RP * j;
+    const bool ok = (r.ok >> j) & 1u;
+    f32x4 v = r.v[j];
+    if constexpr (FUSE) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { const float z = __builtin_fmaf(v[e], sc4[e], sh4[e]); v[e] = z > 0.f ? z : 0.f; }
+    }
+    if (!ok) v = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (j < TM / SP_RP || R < nrows) *(f32x4*)(lds + R * 64 + ((slot ^ (R & 15)) << 2)) = v;
+  }
+}
+
+// One destination class d = (dy << 1) | dx of the tile leaves (conv64_fwd_kernel's flush16, branch-free): through the wave's own 4 KB of
+// the idle slab, 16 tile rows at a time; lane (eg = lane >> 4, eslot = lane & 15) stores channels 4 eslot .. of rows eg + 4 k.
+__device__ __forceinline__ void scatter_flush(const f32x16 (&acc)[2], const float (&bcol)[2], float* __restrict__ S,
+                                              const float* __restrict__ zero4, const int* __restrict__ ri,
+                                              const __amdgpu_buffer_rsrc_t dst, int d, int Wd, f32x4& s4, f32x4& q4) {
+  int tid_f = threadIdx.x;
+  asm volatile("" : "+v"(tid_f));
+  const int lane = tid_f & 63, wrow = tid_f >> 6;
+  const int h = lane >> 5, l31 = lane & 31;
+  const int need = d >> 1 | (d & 1) << 1;  // the rowinfo bits this class needs: the row below / the column to the right exists
+  const unsigned ddelta = (unsigned)((d >> 1) * Wd + (d & 1));
+  const int eg = lane >> 4, eslot = lane & 15;
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+#pragma unroll
+    for (int rr = 0; rr < 8; ++rr) {
+      const int rowl = (rr & 3) + 8 * (rr >> 2) + 4 * h;
+      const int swz = (rowl & 4) << 3;  // 32 for rows 4..7, 12..15 (their two 32-channel halves swapped: bank conflicts)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) S[rowl * 64 + ((32 * j + l31) ^ swz)] = acc[j][8 * half + rr] + bcol[j];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int rowl = eg + 4 * k;
+      const int row = wrow * 32 + 16 * half + rowl;
+      const int w = ri[row];
+      const bool inside = w >= 0 && (w & need) == need;
+      // a lane whose position has no pixel of this class reads four zeros instead (one select on the address, not four on the value):
+      // its store is dropped, and s + 0, fma(0, 0, q) leave the sums as they are, bit for bit (neither sum is ever -0)
+      const f32x4 v = *(const f32x4*)(inside ? S + rowl * 64 + ((eslot ^ ((rowl & 4) << 1)) << 2) : zero4);
+      __builtin_amdgcn_raw_buffer_store_b128(v, dst, inside ? ((unsigned)(w >> 2) + ddelta) * 256u + eslot * 16 : GP_DROP, 0, 0);
+      // (conv64_fwd_kernel's q += v * v is a fused multiply-add at every site: written out, see scatter_land)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { s4[e] += v[e]; q4[e] = __builtin_fmaf(v[e], v[e], q4[e]); }
+    }
+  }
+}
+
+template <bool FUSE>
+__global__ __launch_bounds__(SP_THREADS, 2) void conv64_scatter_pipe_kernel(const float* __restrict__ src_all,
+                                                                           const float* __restrict__ wpack,
+                                                                           const float* __restrict__ bias,
+                                                                           float* __restrict__ dst_all,
+                                                                           float* __restrict__ stats_partial, const ConvProg P,
+                                                                           int ntiles, const float* __restrict__ bnp_all) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  float* As = (float*)smem;                 // (TM + span) x 64, swizzled: the tile's source rows
+  float* Bs = As + (TM + P.span) * 64;      // 64 x 64 weight slab of the current tap; between taps: 4 KB of flush scratch per wave
+  int* rowinfo = (int*)(Bs + 4096);         // [2 (tile parity)][TM]: destination word of a grid position (conv64_fwd_kernel's)
+  unsigned* stab = (unsigned*)(rowinfo + 2 * TM);  // the source-side row table of the tile whose rows are being requested
+  float* frec = (float*)(stab + ST_WORDS);  // [G <= 2][scale 64 | shift 64] of the fused operand
+  float* red = frec + 256;                  // [4 row groups][sum 64 | sum of squares 64]: the tile's BatchNorm partials on their way out
+  float* zero4 = red + 512;                 // four zeros (scatter_flush)
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int nrows = TM + P.span;
+  const int d0 = P.tdst[0], d1 = P.tdst[4], d2 = P.tdst[6], d3 = P.tdst[8];
+
+  const int xcd = blockIdx.x & 7, wi = blockIdx.x >> 3, wpx = gridDim.x >> 3;
+  const int tq = ntiles >> 3, tr = ntiles & 7;
+  const int tbase = (xcd < tr) ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq;
+  const int tcnt = tq + (xcd < tr ? 1 : 0);
+
+  if (tid < 4) zero4[tid] = 0.f;  // (published by the barrier of the first staging)
+  if constexpr (FUSE) {
+    if (tid < 64 * P.G) {
+      const int g = tid >> 6, c = tid & 63;
+      frec[g * 128 + c] = bnp_all[g * 256 + 128 + c];
+      frec[g * 128 + 64 + c] = bnp_all[g * 256 + 192 + c];
+    }
+  }
+  float bcol[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) bcol[j] = bias ? bias[j * 32 + (lane & 31)] : 0.f;
+
+  constexpr int BV = 1024 / SP_THREADS;
+  f32x4 breg[BV];
+  {
+    const f32x4* wsrc = (const f32x4*)(wpack + (size_t)P.tw[0] * 4096);
+#pragma unroll
+    for (int i = 0; i < BV; ++i) breg[i] = wsrc[wave * (BV * 64) + lane + i * 64];
+  }
+  const unsigned dst_bytes = (unsigned)P.dst_gstride * 4u;
+
+  ScatterRows rr;
+  int k = wi;
+  int parity = 0;
+  if (k < tcnt) {  // the first tile's rows are staged the plain way
+    const int tile = tbase + k;
+    const int grp = (P.G > 1 && tile >= P.tpg) ? 1 : 0;  // (G <= 2, checked by the host)
+    const int q0 = (tile - grp * P.tpg) * TM;
+    stab_build(stab, P, q0 + P.min_off, nrows);
+    __syncthreads();  // the table and frec are complete
+    scatter_request(rr, src_all + grp * P.src_gstride, stab);
+    scatter_land<FUSE>(As, rr, nrows, frec + grp * 128);
+  }
+  for (; k < tcnt; k += wpx, parity ^= 1) {
+    const int tile = tbase + k;
+    const int grp = (P.G > 1 && tile >= P.tpg) ? 1 : 0;
+    const int q0 = (tile - grp * P.tpg) * TM;
+    const __amdgpu_buffer_rsrc_t dst = raw_buffer(dst_all + grp * P.dst_gstride, dst_bytes);
+    const int k2 = k + wpx;  // this workgroup's next tile (past the end: this one again, with no rows)
+    const int tile2 = tbase + (k2 < tcnt ? k2 : k);
+    const int grp2 = (P.G > 1 && tile2 >= P.tpg) ? 1 : 0;
+    const int q02 = (tile2 - grp2 * P.tpg) * TM;
+    int* ri = rowinfo + parity * TM;
+    if (tid < TM) {  // (the other parity's copy may still be read by a wave that is flushing the previous tile)
+      const int q = q0 + tid;
+      int w = -1;
+      if (q < P.total_q) {
+        const GridPix g = grid_pix<false>(P, q, P.ds);
+        if (g.y < P.Hd && g.x < P.Wd) w = (((g.n * P.Hd + g.y) * P.Wd + g.x) << 2) | (g.y + 1 < P.Hd ? 1 : 0) | (g.x + 1 < P.Wd ? 2 : 0);
+      }
+      ri[tid] = w;
+    }
+    f32x16 acc[2];
+    f32x4 s4 = {0.f, 0.f, 0.f, 0.f}, q4 = {0.f, 0.f, 0.f, 0.f};
+    int tid_t = tid;  // (one opaque copy of the thread index per tile: see conv64_gather_pipe_kernel)
+    asm volatile("" : "+v"(tid_t));
+    const int lane_t = tid_t & 63, wave_t = tid_t >> 6;
+    const int h_t = lane_t >> 5, l31_t = lane_t & 31;
+    const int arow0 = wave_t * 32 + l31_t - P.min_off;
+    const float* brow = Bs + l31_t * 64;  // column tile j is 32 rows (2048 floats) further
+    const int bkey = lane_t & 15;
+    const int bslot_t = wave_t * (BV * 64) + lane_t;
+    float* S = Bs + wave_t * 1024;
+
+#pragma unroll
+    for (int ti = 0; ti < NTAPS; ++ti) {
+      constexpr f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      const bool first = ti == 0 || ti == 4 || ti == 6 || ti == 8;  // this tap opens a destination class
+      __syncthreads();  // all waves are done with the previous tap's Bs: until its slab write a wave's quarter of it is its scratch
+      if (ti == 4) scatter_flush(acc, bcol, S, zero4, ri, dst, d0, P.Wd, s4, q4);
+      if (ti == 6) scatter_flush(acc, bcol, S, zero4, ri, dst, d1, P.Wd, s4, q4);
+      if (ti == 8) scatter_flush(acc, bcol, S, zero4, ri, dst, d2, P.Wd, s4, q4);
+      {
+        f32x4* wdst = (f32x4*)Bs;
+#pragma unroll
+        for (int i = 0; i < BV; ++i) wdst[bslot_t + i * 64] = breg[i];
+      }
+      {  // the next tap's slab (tap 0 of the next tile behind tap 8: same weights)
+        const f32x4* wsrc = (const f32x4*)(wpack + (size_t)P.tw[(ti + 1) % NTAPS] * 4096);
+#pragma unroll
+        for (int i = 0; i < BV; ++i) breg[i] = wsrc[bslot_t + i * 64];
+      }
+      if (ti == 6) stab_build(stab, P, q02 + P.min_off, k2 < tcnt ? nrows : 0);
+      __syncthreads();
+      if (ti == 7) scatter_request(rr, src_all + grp2 * P.src_gstride, stab);  // the rows of this workgroup's NEXT tile
+      __builtin_amdgcn_sched_barrier(0);  // every request goes out HERE, ahead of the tap's MFMAs
+      const int R = arow0 + P.toff[ti];
+      int abase = (R * 64 + ((h_t ^ (R & 15)) << 2)) * 4;  // bytes; slot (2kc + h) ^ (R & 15) is this XOR (kc << 5)
+      asm volatile("" : "+v"(abase));
+      f32x4 a = *(const f32x4*)((const char*)As + abase);
+      f32x4 b[2];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) b[j] = *(const f32x4*)(brow + j * 2048 + ((h_t ^ bkey) << 2));
+#pragma unroll
+      for (int kc = 0; kc < 8; ++kc) {
+        f32x4 an = a, bn[2] = {b[0], b[1]};
+        if (kc < 7) {
+          an = *(const f32x4*)((const char*)As + (abase ^ ((kc + 1) << 5)));
+#pragma unroll
+          for (int j = 0; j < 2; ++j) bn[j] = *(const f32x4*)(brow + j * 2048 + ((((kc + 1) * 2 + h_t) ^ bkey) << 2));
+        }
+        __builtin_amdgcn_sched_barrier(0);  // keep the prefetch reads ahead of this chunk's MFMAs
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+            acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[r], b[j][r], (first && kc == 0 && r == 0) ? zero16 : acc[j], 0, 0, 0);
+        a = an;
+        b[0] = bn[0]; b[1] = bn[1];
+      }
+    }
+    __syncthreads();  // every wave is done with the last tap's slab and with As: Bs becomes scratch, As takes the next tile
+    scatter_land<FUSE>(As, rr, nrows, frec + grp2 * 128);  // (past the last tile: every row masked off -> zeros)
+    scatter_flush(acc, bcol, S, zero4, ri, dst, d3, P.Wd, s4, q4);
+    if (stats_partial) {
+      // conv64_fwd_kernel's order: the 4 row groups of a wave (lane bits 4, 5), then the 4 waves through LDS
+      int tid_s = tid;
+      asm volatile("" : "+v"(tid_s));
+      const int lane_s = tid_s & 63, wrow_s = tid_s >> 6;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        s4[e] += __shfl_xor(s4[e], 16, 64); s4[e] += __shfl_xor(s4[e], 32, 64);
+        q4[e] += __shfl_xor(q4[e], 16, 64); q4[e] += __shfl_xor(q4[e], 32, 64);
+      }
+      if (lane_s < 16) {
+        *(f32x4*)(red + wrow_s * 128 + lane_s * 4) = s4;
+        *(f32x4*)(red + wrow_s * 128 + 64 + lane_s * 4) = q4;
+      }
+      __syncthreads();
+      if (tid_s < 128) {
+        const float v = red[tid_s] + red[128 + tid_s] + red[256 + tid_s] + red[384 + tid_s];
+        stats_partial[(size_t)tile * 128 + tid_s] = v;  // [0,64): sum, [64,128): sum of squares
+      }
+    }
+  }
+}
+
 }  // namespace
 
 // ---- Which programs these kernels take ----
@@ -849,6 +1135,51 @@ int conv64::launch_gather_pipe(const float* src, const float* wpack, float* dst,
   SRLZ_MAX_LDS(conv64_gather_pipe_kernel, plds);
   SRLZ_LAUNCH(conv64_gather_pipe_kernel, dim3(pgrid), dim3(GP_THREADS), plds, st, src, wpack, dst, stats, ConvProg{P}, ntiles);
   return 0;
+}
+
+// conv64_scatter_pipe_kernel takes the forward program of a stride-2 ConvTranspose — one source class, the destination classes in tap
+// groups {4, 2, 2, 1} — with at most two BatchNorm groups, at most 192 staged rows (PW <= 63), 32-bit buffer offsets and the tile
+// tables' limits of conv64_fwd_kernel, from SCATTER_PIPE_MIN_TILES_PER_GROUP tiles per BatchNorm group on (per group, as above: one
+// group alone and the batched pair take the same kernel — here they would agree bit for bit either way).  Single-kernel timing at
+// N = 512 in two groups, fused operand + bias + statistics, against conv64_fwd_kernel: 111 x 111 (6272 tiles per group) 1011 us against
+// 1102, 55 x 55 (1568) 274 against 291, 27 x 27 (392) 88 against 90; just above the threshold (27 x 27 and 55 x 55 at 261 / 264 tiles
+// per group) 68.1 / 68.6 against 70.6 / 70.7.  Below it the 512 persistent workgroups have about one tile each and nothing to prefetch
+// under: the synchronous kernel keeps those (ConvT1 at bs = 256: 98 tiles per group).
+constexpr int SCATTER_PIPE_MIN_TILES_PER_GROUP = 256;
+bool conv64::scatter_pipe_ok(const Prog& P) {
+  if (P.tpg < SCATTER_PIPE_MIN_TILES_PER_GROUP) return false;
+  bool grouped = P.s2 && P.ss == 1 && P.ds == 2 && !P.dbg;
+  for (int t = 0; t < NTAPS; ++t) grouped = grouped && P.tsrc[t] == 0 && P.tdst[t] == P.tdst[t < 4 ? 0 : t < 6 ? 4 : t < 8 ? 6 : 8];
+  return grouped && P.G <= 2 && fits_32bit_buffer_bytes(P) && fits_32bit_src_floats(P) && fits_32bit_dst_rowinfo(P) &&
+         fits_31bit_grid(P, TM + P.span) && TM + P.span <= SP_RP * SP_BATCH && -P.min_off <= P.PHW;
+}
+
+// The launch of a program scatter_pipe_ok accepts (conv64.hip: launch_fwd); bnp: the fused operand's BatchNorm records or NULL
+int conv64::launch_scatter_pipe(const float* src, const float* wpack, const float* bias, float* dst, float* stats, const float* bnp,
+                                const Prog& P, hipStream_t st) {
+  const int ntiles = P.G * P.tpg;
+  int pgrid = 2 * srlz_device_cus();
+  if (pgrid > ntiles) pgrid = ntiles;
+  pgrid &= ~7;
+  if (pgrid < 8) pgrid = 8;
+  // source rows, slab, rowinfo (two tiles), row table, fused-operand records, statistics on their way out
+  const size_t plds = (size_t)(TM + P.span) * 256 + 16384 + 2 * TM * 4 + ST_WORDS * 4 + 256 * 4 + 512 * 4 + 16;
+  if (bnp) {
+    SRLZ_MAX_LDS(conv64_scatter_pipe_kernel<true>, plds);
+    SRLZ_LAUNCH(conv64_scatter_pipe_kernel<true>, dim3(pgrid), dim3(SP_THREADS), plds, st, src, wpack, bias, dst, stats, ConvProg{P},
+                ntiles, bnp);
+  } else {
+    SRLZ_MAX_LDS(conv64_scatter_pipe_kernel<false>, plds);
+    SRLZ_LAUNCH(conv64_scatter_pipe_kernel<false>, dim3(pgrid), dim3(SP_THREADS), plds, st, src, wpack, bias, dst, stats, ConvProg{P},
+                ntiles, bnp);
+  }
+  return 0;
+}
+
+extern "C" int srlz_conv64_scatter_pipe_supported(const srlz_conv64_desc* d, int backward_data) {
+  ConvProg P;
+  if (backward_data || conv64::with_program(d, 0, &P)) return 0;  // (the data-gradient launches keep conv64_fwd_kernel)
+  return conv64::scatter_pipe_ok(P) ? 1 : 0;
 }
 
 // conv64_bwd_fused_kernel: the same programs without padding (min_off == 0), and at least 8 tiles

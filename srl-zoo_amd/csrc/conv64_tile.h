@@ -45,6 +45,11 @@ int with_program(const srlz_conv64_desc* d, int backward_data, Prog* P);
 // conv64_pipe.hip: does conv64_gather_pipe_kernel take this program (plain operand, no bias), and its launch (launch_fwd decides)
 bool gather_pipe_ok(const Prog& P);
 int launch_gather_pipe(const float* src, const float* wpack, float* dst, float* stats, const Prog& P, hipStream_t st);
+// conv64_pipe.hip: does conv64_scatter_pipe_kernel take this forward program (a stride-2 ConvTranspose's; any bias, plain operand or
+// relu(bn(.)) fused), and its launch
+bool scatter_pipe_ok(const Prog& P);
+int launch_scatter_pipe(const float* src, const float* wpack, const float* bias, float* dst, float* stats, const float* bnp,
+                        const Prog& P, hipStream_t st);
 // conv64_wgrad.hip: the second stage of every weight gradient, conv64_wgrad_reduce over nwg workgroups' partials
 int launch_wgrad_reduce(const float* partial, int nwg, float* dw_ref, float* dbias, int transposed, int interleaved, hipStream_t st);
 

@@ -83,6 +83,7 @@ _PROTOS = {
     "srlz_conv64_bwd_weight_workspace": (c_size_t, [_C64]),
     "srlz_conv64_bwd_fused_supported": (c_int, [_C64]),
     "srlz_conv64_gather_pipe_supported": (c_int, [_C64, c_int]),
+    "srlz_conv64_scatter_pipe_supported": (c_int, [_C64, c_int]),
     "srlz_conv64_bwd_fused_workspace": (c_size_t, [_C64]),
     "srlz_conv64_bwd_fused": (c_int, [P, P, P, _BO, P, P, P, P, P, P, c_size_t, _C64, P]),
     "srlz_conv64_bwd_fused_bn_rows": (c_int, [_C64]),
@@ -247,6 +248,7 @@ _PROTOS = {
 # entry points whose int return value is data, not a status
 _NOT_STATUS = {"srlz_version", "srlz_device_cus", "srlz_conv64_fwd_tiles", "srlz_skinny_tiles", "srlz_convn_fwd_tiles",
                "srlz_convT_out_bwd_fused_tiles", "srlz_convT_out_fwd_loss_workgroups", "srlz_conv64_bwd_fused_supported", "srlz_conv64_gather_pipe_supported",
+               "srlz_conv64_scatter_pipe_supported",
                "srlz_convT_out_bwd_fused_supported",
                "srlz_conv64_bwd_data_tiles", "srlz_conv64_bwd_fused_bn_rows", "srlz_conv64_wino_supported", "srlz_conv64_wino_packed_floats",
                "srlz_conv64_wino_tiles", "srlz_conv64_wino_bwd_data_rows",
