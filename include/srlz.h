@@ -143,6 +143,9 @@ size_t srlz_conv64_bwd_fused_workspace(const srlz_conv64_desc* d);
  * srlz_bn_relu_bwd_sums' separate pass over (x, dx) disappears.  (Channels whose BatchNorm scale is (almost) 0 are summed from x
  * itself by a companion launch inside this call — normally a ~4 us no-op.) */
 int srlz_conv64_bwd_fused_bn_rows(const srlz_conv64_desc* d);
+/* Host only: the persistent workgroups of srlz_conv64_bwd_fused (one per CU, a multiple of 8), which walk the
+ * srlz_conv64_bwd_data_tiles(d) tiles; its workspace holds one weight-gradient partial per workgroup. */
+int srlz_conv64_bwd_fused_workgroups(const srlz_conv64_desc* d);
 int srlz_conv64_bwd_fused(const float* x, const float* x_bnp, const float* dy, const srlz_bn_bwd_operand* dy_bn,
                           const float* wpack_bwd, float* dx, float* dw_ref, float* dbias /* may be NULL */,
                           float* x_bn_bwd_partial /* may be NULL */, void* ws, size_t ws_bytes, const srlz_conv64_desc* d,
@@ -183,6 +186,12 @@ size_t srlz_conv64_bwd_weight_workspace(const srlz_conv64_desc* d);
 int srlz_conv64_bwd_weight(const float* x, const float* dy, float* dw_ref, float* dbias, const float* x_bnp /* as above */,
                            const srlz_bn_bwd_operand* dy_bn /* may be NULL */,
                            void* ws, size_t ws_bytes, const srlz_conv64_desc* d, srlz_stream_t stream);
+/* Host only (no launch): what srlz_conv64_bwd_weight would run for this layer with (has_x_bnp) / without a fused x_bnp and with
+ * (has_dy_bn) / without a gradient rebuilt from (dA, y).  out[0] = the kernel: 0 conv64_wgrad_ring_s2_kernel, 1 conv64_wgrad_ring_kernel,
+ * 2 conv64_wgrad_gather_kernel, 3 conv64_wgrad_kernel (chunk at a time); out[1] = workgroups launched (<= the workspace's);
+ * out[2] = chunks per workgroup — 0 and 1: every workgroup of a BatchNorm group takes that many consecutive chunks, the group's last
+ * one what is left; 2 and 3: the most any workgroup takes, striding over all chunks by out[1]; out[3] = grid positions per chunk. */
+int srlz_conv64_bwd_weight_plan(const srlz_conv64_desc* d, int has_x_bnp, int has_dy_bn, int out[4]);
 
 /* ------------------------------------------------------------------------------------------------------------
  * convN — FORWARD-ONLY 3x3 (pad 1, stride 1/2) and 1x1 (stride 2) convolutions without bias for Cin, Cout multiples of 64:
@@ -223,6 +232,8 @@ typedef struct {
 } srlz_skinny_desc;
 
 int srlz_skinny_tiles(const srlz_skinny_desc* d); /* BN partial records written by conv1 forward */
+/* Host only: the persistent workgroups that walk those tiles in srlz_conv1_fwd(_u8) and srlz_conv1_bwd_weight(_fused(_u8)). */
+int srlz_conv1_workgroups(const srlz_skinny_desc* d);
 /* kind 0 forward: x_nchw [N,C,H,W] -> y_nhwc [N,hf,wf,64]; w_ref [64,C,7,7]. stats_partial as in srlz_conv64_fwd. */
 int srlz_conv1_fwd(const float* x_nchw, const float* w_ref, float* y_nhwc, float* stats_partial,
                    const srlz_skinny_desc* d, srlz_stream_t stream);
@@ -297,6 +308,9 @@ int srlz_convT_out_bwd_fused(const float* dy_nchw, const float* w_ref, float* dx
  * loss_partial[2][srlz_convT_out_fwd_loss_workgroups(d)] = per-frame, per-workgroup sums of squared errors (fp64), to be
  * combined by srlz_pair_loss_finalize.  The gradient is err times a scalar: see srlz_convT_out_bwd_fused / srlz_scale_by_scalar. */
 int srlz_convT_out_fwd_loss_workgroups(const srlz_skinny_desc* d);
+/* Host only: out[0] = jobs (strips of 16 columns), out[1] = persistent workgroups of 4 waves that share them, for srlz_convT_out_fwd /
+ * srlz_convT_out_fwd_loss (backward = 0) or srlz_convT_out_bwd_fused (backward = 1). */
+int srlz_convT_out_os_plan(const srlz_skinny_desc* d, int backward, int out[2]);
 int srlz_convT_out_fwd_loss(const float* x_nhwc, const float* w_ref, const float* bias, const float* target_nchw, float* err_nchw,
                             float* dec_nchw, const float* x_bnp, double* loss_partial, const srlz_skinny_desc* d,
                             srlz_stream_t stream);

@@ -1226,6 +1226,13 @@ extern "C" size_t srlz_conv64_bwd_fused_workspace(const srlz_conv64_desc* d) {
   return (size_t)fused_bwd_grid(P) * WGRAD_PARTIAL_FLOATS * sizeof(float);
 }
 
+// Host only: the persistent workgroups srlz_conv64_bwd_fused launches (they share the srlz_conv64_bwd_data_tiles(d) tiles).
+extern "C" int srlz_conv64_bwd_fused_workgroups(const srlz_conv64_desc* d) {
+  ConvProg P;
+  if (conv64::with_program(d, 1, &P)) return -1;
+  return fused_bwd_grid(P);
+}
+
 extern "C" int srlz_conv64_bwd_fused(const float* x, const float* x_bnp, const float* dy, const srlz_bn_bwd_operand* dy_bn,
                                      const float* wpack_bwd, float* dx, float* dw_ref, float* dbias, float* x_bn_bwd_partial,
                                      void* ws, size_t ws_bytes, const srlz_conv64_desc* d, srlz_stream_t stream) {

@@ -729,7 +729,7 @@ static size_t wgrad_lds_bytes(const ConvProg& P) { return (size_t)(WG_TK + P.spa
 //   chunk    anything else (wider images, a gradient rebuilt from (dA, y)): the chunk-at-a-time conv64_wgrad_kernel.
 // x_bnp: the source is relu(bn(x)); dy_bn_y: the gradient is rebuilt from (dA, y) (srlz_bn_bwd_operand).
 enum class WgradRoute { ring_s2, ring, gather, chunk };
-static WgradRoute wgrad_route(const ConvProg& P, const float* x_bnp, const float* dy_bn_y) {
+static WgradRoute wgrad_route(const ConvProg& P, bool x_bnp, bool dy_bn_y) {
   bool single_src = true;
   for (int t = 1; t < NTAPS; ++t) single_src = single_src && P.tsrc[t] == P.tsrc[0];
   if (single_src && !dy_bn_y && P.s2 && 32 + P.span + 32 <= RING_ROWS_S2) return WgradRoute::ring_s2;
@@ -754,6 +754,35 @@ static int wgrad_grid(const ConvProg& P) {
   return g * P.G;
 }
 
+// What srlz_conv64_bwd_weight launches, decided in one place (srlz_conv64_bwd_weight_plan answers from the same record):
+// nch chunks of tk positions per BatchNorm group on `launched` workgroups.  The ring kernels give every workgroup a contiguous
+// range of cpw chunks (ring re-use of the source rows), group by group, on wpg <= grid / G workgroups per group; the gather and
+// chunk kernels stride over all G * nch chunks by the whole grid (cpw = the most chunks any workgroup takes).
+struct WgradPlan {
+  WgradRoute route;
+  int grid;      // wgrad_grid(P): what the workspace is sized for
+  int launched;  // workgroups launched (<= grid) = partial records for the second stage
+  int nch, tk, cpw, wpg;
+};
+static WgradPlan wgrad_plan(const ConvProg& P, bool x_bnp, bool dy_bn_y) {
+  WgradPlan w;
+  w.route = wgrad_route(P, x_bnp, dy_bn_y);
+  w.grid = wgrad_grid(P);
+  w.tk = w.route == WgradRoute::ring_s2 ? 32 : WG_TK;
+  w.nch = (P.total_q + w.tk - 1) / w.tk;  // per BatchNorm group
+  const int gpg = w.grid / P.G;
+  if (w.route == WgradRoute::ring_s2 || w.route == WgradRoute::ring) {
+    w.cpw = (w.nch + gpg - 1) / gpg;
+    w.wpg = (w.nch + w.cpw - 1) / w.cpw;
+    w.launched = w.wpg * P.G;
+  } else {
+    w.cpw = (w.nch * P.G + w.grid - 1) / w.grid;
+    w.wpg = gpg;
+    w.launched = w.grid;
+  }
+  return w;
+}
+
 }  // namespace
 
 // The second stage behind every kernel that leaves per-workgroup partials: srlz_conv64_bwd_weight below and the fused backward
@@ -771,6 +800,20 @@ extern "C" size_t srlz_conv64_bwd_weight_workspace(const srlz_conv64_desc* d) {
   return (size_t)wgrad_grid(P) * WGRAD_PARTIAL_FLOATS * sizeof(float);
 }
 
+// Host only: the plan srlz_conv64_bwd_weight would launch.  out = {route (0 ring_s2, 1 ring, 2 gather, 3 chunk), workgroups launched,
+// chunks per workgroup, positions per chunk}.
+extern "C" int srlz_conv64_bwd_weight_plan(const srlz_conv64_desc* d, int has_x_bnp, int has_dy_bn, int out[4]) {
+  SRLZ_REQUIRE(out, SRLZ_ERR_NULL, "conv64_bwd_weight_plan: null pointer");
+  ConvProg P;
+  if (int rc = conv64::with_program(d, 0, &P)) return rc;
+  const WgradPlan w = wgrad_plan(P, has_x_bnp != 0, has_dy_bn != 0);
+  out[0] = (int)w.route;
+  out[1] = w.launched;
+  out[2] = w.cpw;
+  out[3] = w.tk;
+  return 0;
+}
+
 extern "C" int srlz_conv64_bwd_weight(const float* x, const float* dy, float* dw_ref, float* dbias, const float* x_bnp,
                                       const srlz_bn_bwd_operand* dy_bn, void* ws, size_t ws_bytes,
                                       const srlz_conv64_desc* d, srlz_stream_t stream) {
@@ -781,40 +824,28 @@ extern "C" int srlz_conv64_bwd_weight(const float* x, const float* dy, float* dw
   SRLZ_REQUIRE(gf.dy_out == nullptr, SRLZ_ERR_BAD_DESC, "conv64_bwd_weight: dy_out is only produced by srlz_conv64_bwd_data");
   const OpFuse xf = OpFuse{x_bnp, nullptr, nullptr, 0.f, 0, nullptr};
   SRLZ_REQUIRE(x && dy && dw_ref && ws, SRLZ_ERR_NULL, "conv64_bwd_weight: null pointer");
-  const int grid = wgrad_grid(P);
-  SRLZ_REQUIRE(ws_bytes >= (size_t)grid * WGRAD_PARTIAL_FLOATS * sizeof(float), SRLZ_ERR_WORKSPACE,
+  const WgradPlan w = wgrad_plan(P, x_bnp != nullptr, gf.y != nullptr);
+  SRLZ_REQUIRE(ws_bytes >= (size_t)w.grid * WGRAD_PARTIAL_FLOATS * sizeof(float), SRLZ_ERR_WORKSPACE,
                "conv64_bwd_weight: workspace too small (%zu bytes)", ws_bytes);
-  const int nchunks = (P.total_q + WG_TK - 1) / WG_TK;  // per BatchNorm group
   hipStream_t st = as_stream(stream);
   float* partial = (float*)ws;
-  int launched_grid = grid, cpw = 0, wpg = 0;
-  // the ring kernels: contiguous chunk ranges per workgroup (ring re-use of the source rows), group by group
-  auto split = [&](int nch) {
-    const int gpg = grid / P.G;
-    cpw = (nch + gpg - 1) / gpg;
-    wpg = (nch + cpw - 1) / cpw;
-    launched_grid = wpg * P.G;
-  };
-  switch (wgrad_route(P, x_bnp, gf.y)) {
+  switch (w.route) {
     case WgradRoute::ring_s2: {
-      const int nch = (P.total_q + 31) / 32;
-      split(nch);
       const size_t lds = (size_t)(RING_S2 + 4 * 32) * 256;
       SRLZ_MAX_LDS(conv64_wgrad_ring_s2_kernel, lds);
-      SRLZ_LAUNCH(conv64_wgrad_ring_s2_kernel, dim3(launched_grid), dim3(256), lds, st, x, dy, partial, P, nch, cpw, wpg, x_bnp);
+      SRLZ_LAUNCH(conv64_wgrad_ring_s2_kernel, dim3(w.launched), dim3(256), lds, st, x, dy, partial, P, w.nch, w.cpw, w.wpg, x_bnp);
       break;
     }
     case WgradRoute::ring: {
-      split(nchunks);
       const size_t lds = (size_t)(RING + 64) * 256 + 2 * 64 * 4;  // ring + gradient rows + the two row tables = 80 KB
       SRLZ_MAX_LDS(conv64_wgrad_ring_kernel, lds);
-      SRLZ_LAUNCH(conv64_wgrad_ring_kernel, dim3(launched_grid), dim3(256), lds, st, x, dy, partial, P, nchunks, cpw, wpg, x_bnp);
+      SRLZ_LAUNCH(conv64_wgrad_ring_kernel, dim3(w.launched), dim3(256), lds, st, x, dy, partial, P, w.nch, w.cpw, w.wpg, x_bnp);
       break;
     }
     case WgradRoute::gather: {
       const size_t lds = wgrad_lds_bytes(P) + (WG_SWORDS + WG_GWORDS) * 4;
       SRLZ_MAX_LDS(conv64_wgrad_gather_kernel, lds);
-      SRLZ_LAUNCH(conv64_wgrad_gather_kernel, dim3(grid), dim3(256), lds, st, x, dy, partial, P, nchunks * P.G);
+      SRLZ_LAUNCH(conv64_wgrad_gather_kernel, dim3(w.launched), dim3(256), lds, st, x, dy, partial, P, w.nch * P.G);
       break;
     }
     case WgradRoute::chunk: {
@@ -822,13 +853,13 @@ extern "C" int srlz_conv64_bwd_weight(const float* x, const float* dy, float* dw
       SRLZ_REQUIRE(lds <= 160 * 1024, SRLZ_ERR_BAD_DESC, "conv64 wgrad: chunk needs %zu bytes of LDS", lds);
       if (P.s2) {
         SRLZ_MAX_LDS((conv64_wgrad_kernel<true, WG_TK>), lds);
-        SRLZ_LAUNCH((conv64_wgrad_kernel<true, WG_TK>), dim3(grid), dim3(256), lds, st, x, dy, partial, P, nchunks * P.G, xf, gf);
+        SRLZ_LAUNCH((conv64_wgrad_kernel<true, WG_TK>), dim3(w.launched), dim3(256), lds, st, x, dy, partial, P, w.nch * P.G, xf, gf);
       } else {
         SRLZ_MAX_LDS((conv64_wgrad_kernel<false, WG_TK>), lds);
-        SRLZ_LAUNCH((conv64_wgrad_kernel<false, WG_TK>), dim3(grid), dim3(256), lds, st, x, dy, partial, P, nchunks * P.G, xf, gf);
+        SRLZ_LAUNCH((conv64_wgrad_kernel<false, WG_TK>), dim3(w.launched), dim3(256), lds, st, x, dy, partial, P, w.nch * P.G, xf, gf);
       }
       break;
     }
   }
-  return conv64::launch_wgrad_reduce(partial, launched_grid, dw_ref, dbias, d->transposed, 0, st);
+  return conv64::launch_wgrad_reduce(partial, w.launched, dw_ref, dbias, d->transposed, 0, st);
 }

@@ -724,6 +724,17 @@ extern "C" int srlz_convT_out_fwd_loss_workgroups(const srlz_skinny_desc* d) {
   return fwd_geo(d).grid;
 }
 
+// Host only: out = {jobs, workgroups} of the output-stationary forward (backward = 0: srlz_convT_out_fwd and _fwd_loss) or of
+// srlz_convT_out_bwd_fused (1).  Wave w of workgroup b takes jobs b * 4 + w, + 4 * workgroups, ...
+extern "C" int srlz_convT_out_os_plan(const srlz_skinny_desc* d, int backward, int out[2]) {
+  if (int rc = os_check(d, "convT_out_os_plan")) return rc;
+  SRLZ_REQUIRE(out, SRLZ_ERR_NULL, "convT_out_os_plan: null pointer");
+  const OsGeo g = backward ? bwd_geo(d) : fwd_geo(d);
+  out[0] = g.njobs;
+  out[1] = g.grid;
+  return 0;
+}
+
 template <typename TT>
 static int os_fwd_loss(const float* x_nhwc, const float* w_ref, const float* bias, const TT* target, const float* lut, float* err_nchw,
                        float* dec_nchw, const float* x_bnp, double* loss_partial, const srlz_skinny_desc* d, srlz_stream_t stream) {

@@ -910,6 +910,13 @@ extern "C" int srlz_skinny_tiles(const srlz_skinny_desc* d) {
   return d->n * ((d->hf + 15) / 16) * ((d->wf + 15) / 16);
 }
 
+// Host only: the persistent workgroups (per channel triple) that walk the srlz_skinny_tiles(d) feature tiles of the conv1 forward and
+// of both conv1 weight gradients.
+extern "C" int srlz_conv1_workgroups(const srlz_skinny_desc* d) {
+  if (check_skinny(d) || d->kind != 0) return -1;
+  return persistent_grid(d->n * ((d->hf + 15) / 16) * ((d->wf + 15) / 16));
+}
+
 extern "C" int srlz_conv1_fwd(const float* x_nchw, const float* w_ref, float* y_nhwc, float* stats_partial,
                               const srlz_skinny_desc* d, srlz_stream_t stream) {
   if (int rc = check_skinny(d)) return rc;

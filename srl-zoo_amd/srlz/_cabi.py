@@ -98,6 +98,10 @@ _PROTOS = {
     "srlz_conv64_wino_bwd_data_rows": (c_int, [_C64]),
     "srlz_conv64_wino_bwd_data_pool_sums": (c_int, [P, P, P, P, P, P, P, _PD, P, _C64, P]),
     "srlz_conv64_bwd_weight": (c_int, [P, P, P, P, P, _BO, P, c_size_t, _C64, P]),
+    "srlz_conv64_bwd_weight_plan": (c_int, [_C64, c_int, c_int, POINTER(c_int)]),
+    "srlz_conv64_bwd_fused_workgroups": (c_int, [_C64]),
+    "srlz_conv1_workgroups": (c_int, [_SK]),
+    "srlz_convT_out_os_plan": (c_int, [_SK, c_int, POINTER(c_int)]),
     "srlz_conv64_debug_program": (c_int, [_C64, c_int, POINTER(c_int), c_int]),
     "srlz_linear_debug_route": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_size_t, POINTER(c_int)]),
     "srlz_debug_placement": (c_int, [P, c_int, c_int, c_int, P]),
@@ -254,7 +258,7 @@ _NOT_STATUS = {"srlz_version", "srlz_device_cus", "srlz_conv64_fwd_tiles", "srlz
                "srlz_conv64_wino_tiles", "srlz_conv64_wino_bwd_data_rows",
                "srlz_conv64_debug_program", "srlz_comm_world", "srlz_dense_supported",
                "srlz_dense_out_fwd_loss_workgroups", "srlz_reward_probe_chunk_rows", "srlz_infer_block_supported",
-               "srlz_infer_tile"}
+               "srlz_infer_tile", "srlz_conv64_bwd_fused_workgroups", "srlz_conv1_workgroups"}
 
 EXPORTED = sorted(_PROTOS.keys())
 
