@@ -234,6 +234,12 @@ typedef struct {
 int srlz_skinny_tiles(const srlz_skinny_desc* d); /* BN partial records written by conv1 forward */
 /* Host only: the persistent workgroups that walk those tiles in srlz_conv1_fwd(_u8) and srlz_conv1_bwd_weight(_fused(_u8)). */
 int srlz_conv1_workgroups(const srlz_skinny_desc* d);
+/* Host only: 1 when srlz_conv1_fwd(_u8) and srlz_conv1_bwd_weight_fused(_u8) stage their image windows through a buffer resource
+ * (32-bit offsets from a scalar base, out-of-image elements dropped by the hardware's range check), 0 when they keep the
+ * generic-pointer staging: C = 3 and kind 0 only, the image tensor — judged as floats — below 2^32 bytes (with the few rows the first
+ * window starts in front of it), one image plane below 2^24 bytes and one image's feature map below 2^32 bytes.  The results are the
+ * same bits either way (srlz_debug_conv1_*_generic run the generic staging regardless). */
+int srlz_conv1_buffer_staging_supported(const srlz_skinny_desc* d);
 /* kind 0 forward: x_nchw [N,C,H,W] -> y_nhwc [N,hf,wf,64]; w_ref [64,C,7,7]. stats_partial as in srlz_conv64_fwd. */
 int srlz_conv1_fwd(const float* x_nchw, const float* w_ref, float* y_nhwc, float* stats_partial,
                    const srlz_skinny_desc* d, srlz_stream_t stream);
@@ -908,6 +914,20 @@ int srlz_debug_mfma_valu(float* out, int blocks, int iters, int valu_per_mfma, i
 /* Debug: out[4*b..] = {XCC id, HW_ID register, start clock, end clock} of workgroup b of a launch whose workgroups each
  * hold lds_bytes of LDS and spin for `spin` ticks (how the dispatcher places / replaces co-resident workgroups). */
 int srlz_debug_placement(unsigned* out, int blocks, int lds_bytes, int spin, srlz_stream_t stream);
+/* srlz_conv1_fwd(_u8) and srlz_conv1_bwd_weight_fused(_u8) through the generic-pointer window staging, whatever
+ * srlz_conv1_buffer_staging_supported says: the reference the buffer staging is compared with, bit for bit.  Arguments as theirs. */
+int srlz_debug_conv1_fwd_generic(const float* x_nchw, const float* w_ref, float* y_nhwc, float* stats_partial,
+                                 const srlz_skinny_desc* d, srlz_stream_t stream);
+int srlz_debug_conv1_fwd_u8_generic(const uint8_t* x_u8, const float* norm_lut, const float* w_ref, float* y_nhwc,
+                                    float* stats_partial, const srlz_skinny_desc* d, srlz_stream_t stream);
+int srlz_debug_conv1_bwd_weight_fused_generic(const float* x_nchw, const float* y_nhwc, const float* bnp, const uint8_t* argmax,
+                                              const float* dpooled, const float* sums, int training, float* dw_ref, void* ws,
+                                              size_t ws_bytes, const srlz_skinny_desc* d, const struct srlz_pool_desc_s* pd,
+                                              srlz_stream_t stream);
+int srlz_debug_conv1_bwd_weight_fused_u8_generic(const uint8_t* x_u8, const float* norm_lut, const float* y_nhwc, const float* bnp,
+                                                 const uint8_t* argmax, const float* dpooled, const float* sums, int training,
+                                                 float* dw_ref, void* ws, size_t ws_bytes, const srlz_skinny_desc* d,
+                                                 const struct srlz_pool_desc_s* pd, srlz_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,7 @@
 // 48-column convT GEMM).  Channels are processed in groups of 3 (C=6/9 multi-view loops over groups).
 #include "common.h"
 #include <stdlib.h>
+#include <type_traits>
 
 namespace {
 
@@ -69,6 +70,7 @@ struct ImgRegs {
   static constexpr int TOT = 3 * Geo<K, TR>::ROWS * Geo<K, TR>::COLS;
   static constexpr int PER = (TOT + 255) / 256;
   int pk[PER];       // (LDS offset of the element << 14) | (c << 12) | (row << 6) | xl, or -1 past the end of the window
+  unsigned voff[PER];  // buffer staging only (image_index_buf<.., VOFF = true>): the element's byte offset from the window's origin
   float v[PER];      // raw loads (from a clamped address when the element is outside the image)
   unsigned inside;   // bit j: element j is inside the image; applied when the value LANDS — a select (or a branch merge) at the
                      // request would make the compiler wait for the load right there, and nothing would travel under the MFMAs
@@ -110,6 +112,8 @@ __device__ __forceinline__ bool image_decode(const ImgRegs<K, TR>& r, int j, int
   return pk >= 0;
 }
 
+// GENERIC-POINTER staging: every launch but conv1's K = 7, C = 3 ones, which stage through a buffer resource (image_request_buf below)
+// and keep this one as their reference (srlz_debug_conv1_*_generic).
 // HOIST = true: the unpacked decomposition may live in registers for the whole kernel (no opaque copy): ~35 more registers, ~270
 // fewer VALU instructions per tile — worth it where the registers exist (conv1 forward: 1.10 vs 1.16 ms).
 // PT = uint8_t: the frames are still the loader's bytes ([N,C,W,H] planar, /root/reference/preprocessing/data_loader.py:255 applied
@@ -125,8 +129,10 @@ __device__ __forceinline__ void image_request(ImgRegs<K, TR>& r, const PT* __res
     int c, row, xl;
     const bool live = image_decode<K, HOIST, TR>(r, j, c, row, xl);
     const int iy = iy0 + row, ix = ix0 + xl;
-    // every instruction here is paid for in MFMA time: 32-bit element offsets from the uniform base (the host checks
-    // that the tensor has fewer than 2^31 elements), one unsigned compare per axis, a select instead of a masked 64-bit address chain
+    // every instruction here is paid for in MFMA time: one unsigned compare per axis and a select instead of a masked
+    // address chain.  The element offset is 32-bit (the host checks that the tensor has fewer than 2^31 elements), but it is added to a
+    // generic pointer per element — a 64-bit add, and with the bounds test, the select and the `inside` bit about 30 instructions per
+    // element; image_request_buf is what the flagship's shape runs instead.
     const bool ok = valid && live && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
     const unsigned off = ((unsigned)(plane0 + c) * (unsigned)H + (unsigned)iy) * (unsigned)W + (unsigned)ix;
     const PT raw = img[ok ? off : 0u];
@@ -172,13 +178,131 @@ __device__ __forceinline__ void image_land(float* __restrict__ T, const ImgRegs<
   }
 }
 
+// BUFFER staging (conv1, K = 7 and C = 3: srlz_conv1_buffer_staging_supported).  The element's address splits into the wave-uniform
+// origin of the tile's window, ((n*C + 3*cg)*H + iy0)*W + ix0, which moves the BASE of a buffer resource with scalar arithmetic, and the
+// tile-independent offset of the element inside the window, (c*H + row)*W + xl, which is the load's vector offset: no 64-bit
+// arithmetic per element.  The resource ends where the tensor ends (and has no bytes at all for "no next tile").  The range check of a
+// raw buffer applies to the vector (+ instruction) offset only, NOT to the scalar one, so the origin goes into the base and an
+// element that must not be read gets the vector offset IMG_DROP, beyond any resource: the load returns 0 without touching memory —
+// the zero padding itself on floats, so `inside` exists for bytes only (byte 0 is not value 0).  A window that lies inside the image
+// (25 of the 49 tiles of a 224 x 224 image; wave-uniform) is requested with no test at all.
+constexpr unsigned IMG_DROP = 0xFFFFFF00u;
+
+// The kernels take the staging with their pixel type: BufStaged<T> = pixels of type T through the buffer staging.
+template <typename T> struct BufStaged {};
+template <typename T> struct Pixel { using type = T; static constexpr bool buf = false; };
+template <typename T> struct Pixel<BufStaged<T>> { using type = T; static constexpr bool buf = true; };
+
+// VOFF: the byte offsets live in registers for the whole kernel (a request is one instruction per element on an interior tile);
+// otherwise they are rebuilt from pk with two multiply-adds.  Past the end of the window: the spare float, window element (0, 0, 0)
+// (inside the image whenever it passes the border test) and, with VOFF, IMG_DROP.
+template <int K, typename PT, bool VOFF, int TR = 16, int XPV = XP, int PPV = Geo<K, TR>::PP>
+__device__ __forceinline__ void image_index_buf(ImgRegs<K, TR>& r, int H, int W) {
+  constexpr int ROWS = Geo<K, TR>::ROWS, COLS = Geo<K, TR>::COLS, TOT = ImgRegs<K, TR>::TOT;
+  static_assert(6 * PPV < (1 << 17) && ROWS < 64 && COLS < 64, "pk: 17 bits of LDS offset, 6 bits per window axis");
+#pragma unroll
+  for (int j = 0; j < ImgRegs<K, TR>::PER; ++j) {
+    const int idx = threadIdx.x + 256 * j;
+    const int c = idx / (ROWS * COLS);
+    const int rem = idx - c * (ROWS * COLS);
+    const int row = rem / COLS, xl = rem - row * COLS;
+    const int dst = (c * 2 + (xl & 1)) * PPV + row * XPV + (xl >> 1);
+    r.pk[j] = idx < TOT ? ((dst << 14) | (c << 12) | (row << 6) | xl) : ((PPV - 1) << 14);
+    if constexpr (VOFF) r.voff[j] = idx < TOT ? (unsigned)((c * H + row) * W + xl) * (unsigned)sizeof(PT) : IMG_DROP;
+  }
+}
+
+// `elems`: elements of the whole image tensor (what the resource may reach).
+template <int K, int PAD, typename PT, bool VOFF, int TR = 16>
+__device__ __forceinline__ void image_request_buf(ImgRegs<K, TR>& r, const PT* __restrict__ img, long long elems, int n, int C, int cg,
+                                                  int H, int W, int oy0, int ox0, bool valid) {
+  constexpr int ROWS = Geo<K, TR>::ROWS, COLS = Geo<K, TR>::COLS, PER = ImgRegs<K, TR>::PER;
+  constexpr bool U8 = sizeof(PT) == 1;
+  const int iy0 = 2 * oy0 - PAD, ix0 = 2 * ox0 - PAD;
+  // (all scalar) origin of the window; up to PAD rows and columns in front of the tensor for the first tiles of image 0, whose
+  // elements there fail the border test
+  const long long org = valid ? ((long long)(n * C + cg * 3) * H + iy0) * W + ix0 : 0;
+  const __amdgpu_buffer_rsrc_t rs = raw_buffer(img + org, valid ? (unsigned)((elems - org) * (long long)sizeof(PT)) : 0u);
+  [[maybe_unused]] const int HW4 = H * W * (int)sizeof(PT), W4 = W * (int)sizeof(PT);
+  auto fetch = [&](int j, unsigned off) {
+    if constexpr (U8) r.v[j] = __uint_as_float((unsigned)__builtin_amdgcn_raw_buffer_load_b8(rs, off, 0, 0));
+    else r.v[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0));
+  };
+  auto offset_of = [&](int j, int pk) -> unsigned {
+    if constexpr (VOFF) return r.voff[j];
+    else return mad_u24((unsigned)(pk >> 6) & 63u, W4, mad_u24((unsigned)(pk >> 12) & 3u, HW4, ((unsigned)pk & 63u) * (unsigned)sizeof(PT)));
+  };
+  r.inside = ~0u;
+  if (iy0 >= 0 && ix0 >= 0 && iy0 + ROWS <= H && ix0 + COLS <= W) {  // interior tile
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+      int pk = r.pk[j];
+      if constexpr (!VOFF) asm volatile("" : "+v"(pk));  // (see ImgRegs: the unpacking stays inside the tile loop)
+      fetch(j, offset_of(j, pk));
+    }
+  } else {
+    // window rows [ylo, ylo + ycnt) and columns [xlo, xlo + xcnt) are inside the image: one unsigned compare per axis
+    const int ylo = iy0 < 0 ? -iy0 : 0, xlo = ix0 < 0 ? -ix0 : 0;
+    const unsigned ycnt = (unsigned)((H - iy0 < ROWS ? H - iy0 : ROWS) - ylo), xcnt = (unsigned)((W - ix0 < COLS ? W - ix0 : COLS) - xlo);
+    if constexpr (U8) r.inside = 0;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+      int pk = r.pk[j];
+      asm volatile("" : "+v"(pk));
+      const bool ok = (unsigned)(((pk >> 6) & 63) - ylo) < ycnt && (unsigned)((pk & 63) - xlo) < xcnt;
+      fetch(j, ok ? offset_of(j, pk) : IMG_DROP);
+      if constexpr (U8) r.inside |= (ok ? 1u : 0u) << j;
+    }
+  }
+}
+
+// (the pitches are those image_index_buf was given)
+template <int K, bool U8, int TR = 16>
+__device__ __forceinline__ void image_land_buf(float* __restrict__ T, const ImgRegs<K, TR>& r, const float* __restrict__ lut = nullptr) {
+  float val[ImgRegs<K, TR>::PER];
+#pragma unroll
+  for (int j = 0; j < ImgRegs<K, TR>::PER; ++j) {  // (bytes: all look-ups requested before the first one is used)
+    if constexpr (U8) {
+      int pk = r.pk[j];
+      asm volatile("" : "+v"(pk));
+      val[j] = lut[((pk >> 12) & 3) * 256 + (int)__float_as_uint(r.v[j])];
+    } else {
+      val[j] = r.v[j];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < ImgRegs<K, TR>::PER; ++j) {
+    int dst = r.pk[j];
+    asm volatile("" : "+v"(dst));
+    dst = (int)((unsigned)dst >> 14);
+    if constexpr (U8) T[dst] = ((r.inside >> j) & 1u) ? val[j] : 0.f;
+    else T[dst] = val[j];
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // feat[n,oy,ox,:] = sum_{c,ky,kx} img[n,c,2oy-PAD+ky,2ox-PAD+kx] * w_ref[:,c,ky,kx]      (w_ref: [64][C][K][K])
 // 256 threads, tile = 16x16 output pixels; wave w owns tile rows 4w..4w+3 (two 32-pixel M-tiles) x 64 channels.
 // Persistent over tiles; for C == 3 the 64 x KT weight matrix is staged in LDS once per workgroup.
 // ------------------------------------------------------------------------------------------------------------------
-template <int K, int PAD, bool BNBWD = false, bool MULTI = false, typename PT = float>
-__global__ __launch_bounds__(256, 2) void skinny_conv_kernel(const PT* __restrict__ img,
+// The forward kernel's staging: buffer (BUF) or generic-pointer.
+template <int K, int PAD, typename PT, bool BUF>
+__device__ __forceinline__ void conv_request(ImgRegs<K>& nx, const PT* __restrict__ img, long long elems, int n, int C, int cg, int H,
+                                             int W, int oy0, int ox0, bool valid) {
+  if constexpr (BUF) image_request_buf<K, PAD, PT, true>(nx, img, elems, n, C, cg, H, W, oy0, ox0, valid);
+  else image_request<K, PAD, false>(nx, img, n, C, cg, H, W, oy0, ox0, valid);
+}
+template <int K, bool HOIST, bool U8, bool BUF>
+__device__ __forceinline__ void conv_land(float* __restrict__ T, const ImgRegs<K>& nx, const float* __restrict__ lut) {
+  if constexpr (BUF) image_land_buf<K, U8>(T, nx, lut);
+  else image_land<K, HOIST, 16, U8>(T, nx, 1.f, lut);
+}
+
+// BUF: buffer staging of the image window (image_request_buf) and the per-tile trims that go with it — conv1 with C = 3 only.
+// It is selected by the pixel type: PTAG = float / uint8_t is the generic-pointer staging (and those instantiations keep their names),
+// PTAG = BufStaged<float> / BufStaged<uint8_t> the buffer staging of the same pixels.
+template <int K, int PAD, bool BNBWD = false, bool MULTI = false, typename PTAG = float>
+__global__ __launch_bounds__(256, 2) void skinny_conv_kernel(const typename Pixel<PTAG>::type* __restrict__ img,
                                                             const float* __restrict__ w_ref,
                                                             float* __restrict__ feat,
                                                             float* __restrict__ stats_partial, int N, int C, int H,
@@ -186,7 +310,10 @@ __global__ __launch_bounds__(256, 2) void skinny_conv_kernel(const PT* __restric
                                                             const float* __restrict__ y_raw,
                                                             const float* __restrict__ y_bnp, int npg,
                                                             const float* __restrict__ lut = nullptr) {
+  using PT = typename Pixel<PTAG>::type;
+  constexpr bool BUF = Pixel<PTAG>::buf;
   constexpr bool U8 = sizeof(PT) == 1;  // uint8 frames + the normalisation table (image_land)
+  static_assert(!BUF || (K == 7 && !BNBWD && !MULTI), "buffer staging: conv1 forward with one channel group");
   // npg = images per BatchNorm group (N when there is one group): image n uses the record y_bnp[(n / npg) * 256 ..]
   // BNBWD (data-gradient use, kind 1; y_raw != NULL): `feat` is dA = d(loss)/d(relu(bn(y_raw))) and the per-tile partials become
   // the two BatchNorm-backward sums  sum dz  and  sum dz*xhat  (dz = dA*[bn(y)>0]) instead of  sum v  and  sum v^2 —
@@ -213,8 +340,9 @@ __global__ __launch_bounds__(256, 2) void skinny_conv_kernel(const PT* __restric
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = lane >> 5, l31 = lane & 31;
-  const int ncg = C / 3;
+  const int ncg = BUF ? 1 : C / 3;
   const int ntiles = N * tiles_y * tiles_x;
+  [[maybe_unused]] const long long img_elems = (long long)N * C * H * W;
 
   auto stage_weights = [&](int cg) {
     for (int idx = tid; idx < KS * 128; idx += 256) {
@@ -236,13 +364,14 @@ __global__ __launch_bounds__(256, 2) void skinny_conv_kernel(const PT* __restric
   const float* wl0 = Wl + h * 64 + l31;
 
   ImgRegs<K> nx;
-  image_index<K>(nx);
+  if constexpr (BUF) image_index_buf<K, PT, true>(nx, H, W);
+  else image_index<K>(nx);
   if (PIPE && (int)blockIdx.x < ntiles) {  // the first window is staged the plain way
     const int t0 = vtile(blockIdx.x, ntiles);
     const int n = t0 / (tiles_y * tiles_x);
     const int trem = t0 - n * (tiles_y * tiles_x);
-    image_request<K, PAD, false>(nx, img, n, C, 0, H, W, (trem / tiles_x) * 16, (trem % tiles_x) * 16, true);
-    image_land<K, HOIST, 16, U8>(T, nx, 1.f, lut);
+    conv_request<K, PAD, PT, BUF>(nx, img, img_elems, n, C, 0, H, W, (trem / tiles_x) * 16, (trem % tiles_x) * 16, true);
+    conv_land<K, HOIST, U8, BUF>(T, nx, lut);
     if (MULTI) stage_weights(0);
   }
   for (int v = blockIdx.x; v < ntiles; v += gridDim.x) {
@@ -251,12 +380,14 @@ __global__ __launch_bounds__(256, 2) void skinny_conv_kernel(const PT* __restric
     const int trem = tile - n * (tiles_y * tiles_x);
     const int oy0 = (trem / tiles_x) * 16, ox0 = (trem % tiles_x) * 16;
     f32x16 acc[2][2];
+    if constexpr (!BUF) {  // (BUF: the first k-step's MFMAs take C = 0 instead)
 #pragma unroll
-    for (int a = 0; a < 2; ++a)
+      for (int a = 0; a < 2; ++a)
 #pragma unroll
-      for (int b = 0; b < 2; ++b)
+        for (int b = 0; b < 2; ++b)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+          for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+    }
     // Epilogue layout: lane (g = lane >> 4, slot = lane & 15) owns channels [4*slot, 4*slot+4) of pixel column 4*it + g of tile
     // row  wave*4 + rowq  (rowq = 0..3, it = 0..3): every global access of the epilogue is a 16-byte one (a dword-per-lane
     // access pattern sustains only ~5 B/cycle/CU here — it was the bound of the ConvTranspose-5 data gradient).
@@ -272,10 +403,10 @@ __global__ __launch_bounds__(256, 2) void skinny_conv_kernel(const PT* __restric
         if (cg2 == ncg) { cg2 = 0; tile2 = vtile(v + gridDim.x, ntiles); }
         const int n2 = tile2 / (tiles_y * tiles_x);
         const int trem2 = tile2 - n2 * (tiles_y * tiles_x);
-        image_request<K, PAD, false>(nx, img, n2, C, cg2, H, W, (trem2 / tiles_x) * 16, (trem2 % tiles_x) * 16, tile2 < ntiles);
+        conv_request<K, PAD, PT, BUF>(nx, img, img_elems, n2, C, cg2, H, W, (trem2 / tiles_x) * 16, (trem2 % tiles_x) * 16, tile2 < ntiles);
       } else {
-        image_request<K, PAD, false>(nx, img, n, C, cg, H, W, oy0, ox0, true);
-        image_land<K, HOIST, 16, U8>(T, nx, 1.f, lut);
+        conv_request<K, PAD, PT, BUF>(nx, img, img_elems, n, C, cg, H, W, oy0, ox0, true);
+        conv_land<K, HOIST, U8, BUF>(T, nx, lut);
         if (MULTI) stage_weights(cg);
       }
       if (BNBWD && (!MULTI || cg == 0)) {  // (after the image loads: they are waited for first, these stay in flight behind the MFMAs)
@@ -296,6 +427,10 @@ __global__ __launch_bounds__(256, 2) void skinny_conv_kernel(const PT* __restric
         const int ko = h ? koff<K>(KS + s) : koff<K>(s);
         const float a0 = T[pb0 + ko], a1 = T[pb1 + ko];
         const float b0 = wl0[s * 128], b1 = wl0[s * 128 + 32];
+        if (BUF && s == 0) {  // (one channel group: this is the tile's first k-step)
+          const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+          acc[0][0] = acc[0][1] = acc[1][0] = acc[1][1] = zero;
+        }
         acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
         acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
         acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
@@ -303,7 +438,7 @@ __global__ __launch_bounds__(256, 2) void skinny_conv_kernel(const PT* __restric
       }
       if (PIPE) {
         __syncthreads();  // every wave is done reading T (and Wl): the next window lands
-        image_land<K, HOIST, 16, U8>(T, nx, 1.f, lut);
+        conv_land<K, HOIST, U8, BUF>(T, nx, lut);
         if (MULTI) stage_weights(cg2);
       }
     }
@@ -321,6 +456,10 @@ __global__ __launch_bounds__(256, 2) void skinny_conv_kernel(const PT* __restric
 #pragma unroll
       for (int i = 0; i < 16; ++i) asm volatile("" : "+v"(yv[BNBWD ? i : 0]));
     }
+    // BUF: the map of image n as a buffer resource.  FULL (wave-uniform; BUF only): the tile lies inside the feature map
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t feat_rs = raw_buffer(feat + (size_t)n * HF * WF * 64, BUF ? (unsigned)(HF * WF * 256) : 0u);
+    auto flush = [&](auto FULL) __attribute__((always_inline)) {
+    constexpr bool full = decltype(FULL)::value;
 #pragma unroll
     for (int rowq = 0; rowq < 4; ++rowq) {
       const int mt = rowq >> 1, half = rowq & 1;
@@ -339,8 +478,23 @@ __global__ __launch_bounds__(256, 2) void skinny_conv_kernel(const PT* __restric
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
         const int pl = it * 4 + eg, ox = ox0 + pl;
-        const f32x4 v = *(const f32x4*)(Ew + pl * 64 + eslot * 4);
-        if (oy < HF && ox < WF) {
+        f32x4 v = *(const f32x4*)(Ew + pl * 64 + eslot * 4);
+        if constexpr (BUF) {
+          // branch-free: a pixel outside the feature map stores to IMG_DROP, beyond the image's resource, and contributes exactly
+          // nothing to the statistics (v = 0: s + 0 == s bit for bit, s is never -0); a tile that lies inside the map (wave-uniform,
+          // every tile of a 112 x 112 map) pays for neither
+          unsigned off = (unsigned)((oy * WF + ox) * 256 + eslot * 16);
+          if constexpr (!full) {
+            const bool ok = oy < HF && ox < WF;
+            off = ok ? off : IMG_DROP;
+            v = ok ? v : f32x4{0.f, 0.f, 0.f, 0.f};
+          }
+          __builtin_amdgcn_raw_buffer_store_b128(v, feat_rs, off, 0, 0);
+          // (the fused multiply-add spelled out: left to contract  0 + v0*v0 + v1*v1  itself, hipcc pairs the first two squares either
+          // way round depending on the code around them, and the records would differ from the generic staging's in the last bit)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { s1[e] += v[e]; s2[e] = __builtin_fmaf(v[e], v[e], s2[e]); }
+        } else if (oy < HF && ox < WF) {
           *(f32x4*)(feat + ((size_t)(n * HF + oy) * WF + ox) * 64 + eslot * 4) = v;
           if (BNBWD) {
             const f32x4 yy = yv[BNBWD ? rowq * 4 + it : 0];
@@ -354,6 +508,9 @@ __global__ __launch_bounds__(256, 2) void skinny_conv_kernel(const PT* __restric
         }
       }
     }
+    };
+    if (BUF && oy0 + 16 <= HF && ox0 + 16 <= WF) flush(std::true_type{});
+    else flush(std::false_type{});
     if (stats_partial) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -498,13 +655,17 @@ __constant__ unsigned char TAP7[160] = {
 // address-path bound (measured 2 TB/s).  Wave w owns M-tile (w&1), ALL N-tiles and 64 of a half's 128 pixels.
 // Persistent over tiles; each (workgroup, w>>1) writes its own partial [64][NT*32] -> skinny_wgrad_reduce.
 // ------------------------------------------------------------------------------------------------------------------
-template <int K, int PAD, bool FUSED = false, typename PT = float>
-__global__ __launch_bounds__(256, 2) void skinny_wgrad_kernel(const PT* __restrict__ img,
+// BUF: buffer staging of the image window (image_request_buf; no registers to spare here: the offsets are rebuilt from pk).
+// Selected by the pixel type, as in skinny_conv_kernel: PTAG = BufStaged<float> / BufStaged<uint8_t>.
+template <int K, int PAD, bool FUSED = false, typename PTAG = float>
+__global__ __launch_bounds__(256, 2) void skinny_wgrad_kernel(const typename Pixel<PTAG>::type* __restrict__ img,
                                                              const float* __restrict__ feat,
                                                              float* __restrict__ partial, int N, int C, int H, int W,
                                                              int HF, int WF, int tiles_y, int tiles_x,
                                                              const float* __restrict__ feat_bnp, const PoolFuse pf, int npg,
                                                              const float* __restrict__ lut = nullptr) {
+  using PT = typename Pixel<PTAG>::type;
+  constexpr bool BUF = Pixel<PTAG>::buf;
   constexpr bool U8 = sizeof(PT) == 1;  // uint8 frames + the normalisation table (image_land)
   // FUSED (K = 7): the feature operand is rebuilt from (y, argmax, dpooled) by the BatchNorm + ReLU + MaxPool backward (PoolFuse)
   // npg = images per BatchNorm group: image n uses the records feat_bnp / pf.bnp [(n / npg) * 256 ..], pf.sums [(n / npg) * 128 ..]
@@ -672,11 +833,17 @@ __global__ __launch_bounds__(256, 2) void skinny_wgrad_kernel(const PT* __restri
     }
   };
   ImgRegs<K> ir;  // the image window of the next tile, requested during the last stage of this one
-  image_index<K, 16, WXP, WPP>(ir);
+  static_assert(!BUF || (K == 7 && FUSED), "buffer staging: the fused conv1 weight gradient");
+  if constexpr (BUF) image_index_buf<K, PT, false, 16, WXP, WPP>(ir, H, W);
+  else image_index<K, 16, WXP, WPP>(ir);
+  [[maybe_unused]] const long long img_elems = (long long)N * C * H * W;
   auto i_request = [&](int tile_) {
     const int n_ = tile_ / tpi;
     const int trem_ = tile_ - n_ * tpi;
-    image_request<K, PAD, K == 4>(ir, img, n_, C, cg, H, W, (trem_ / tiles_x) * 16, (trem_ % tiles_x) * 16, tile_ < ntiles);
+    if constexpr (BUF)
+      image_request_buf<K, PAD, PT, false>(ir, img, img_elems, n_, C, cg, H, W, (trem_ / tiles_x) * 16, (trem_ % tiles_x) * 16, tile_ < ntiles);
+    else
+      image_request<K, PAD, K == 4>(ir, img, n_, C, cg, H, W, (trem_ / tiles_x) * 16, (trem_ % tiles_x) * 16, tile_ < ntiles);
   };
   if ((int)blockIdx.x < ntiles) { f_request(vtile(blockIdx.x, ntiles), 0); i_request(vtile(blockIdx.x, ntiles)); }
   for (int v = blockIdx.x; v < ntiles; v += gridDim.x) {
@@ -705,7 +872,10 @@ __global__ __launch_bounds__(256, 2) void skinny_wgrad_kernel(const PT* __restri
 #pragma unroll 1
     for (int half = 0; half < NSTAGE; ++half) {
       __syncthreads();
-      if (half == 0) image_land<K, K == 4, 16, U8, WXP, WPP>(T, ir, 1.f, lut);
+      if (half == 0) {
+        if constexpr (BUF) image_land_buf<K, U8>(T, ir, lut);
+        else image_land<K, K == 4, 16, U8, WXP, WPP>(T, ir, 1.f, lut);
+      }
       f_resolve();
       __syncthreads();
       if (half + 1 < NSTAGE) f_request(tile, half + 1);
@@ -841,21 +1011,37 @@ static int persistent_grid(int ntiles) {
   return g > ntiles ? ntiles : g;
 }
 
+// The window staging through a buffer resource (image_request_buf) and the forward's buffer stores: conv1 with one channel triple, the
+// image tensor (judged as floats) plus the rows the first window starts in front of it within a resource's 32-bit range and below
+// IMG_DROP, one image's plane products within mad_u24's 24 bits, and one image's feature map below IMG_DROP as well.
+static bool buffer_staging_ok(const srlz_skinny_desc* d) {
+  if (d->kind != 0 || d->c != 3) return false;
+  const long long bytes = (long long)d->n * d->c * d->himg * d->wimg * 4, lead = (3LL * d->wimg + 3) * 4;
+  return bytes + lead <= (long long)IMG_DROP && (long long)d->himg * d->wimg * 4 < (1LL << 24) &&
+         (long long)d->hf * d->wf * 256 <= (long long)IMG_DROP;
+}
+
+// generic: the generic-pointer staging where the buffer staging would run (the srlz_debug_conv1_*_generic reference entries)
 template <int K, int PAD, typename PT = float>
 static int launch_conv(const PT* img, const float* w, float* feat, float* stats, const srlz_skinny_desc* d, hipStream_t st,
-                       const float* y_raw = nullptr, const float* y_bnp = nullptr, const float* lut = nullptr) {
+                       const float* y_raw = nullptr, const float* y_bnp = nullptr, const float* lut = nullptr, bool generic = false) {
   const int ty = (d->hf + 15) / 16, tx = (d->wf + 15) / 16;
   const int ntiles = d->n * ty * tx;
   const bool multi = d->c > 3;
   const dim3 grid(persistent_grid(ntiles)), block(256);
-#define SRLZ_CONV_LAUNCH(BN, MU, PIPED)                                                                                   \
+#define SRLZ_CONV_LAUNCH_KERNEL(KERNEL, PIPED)                                                                            \
   do {                                                                                                                    \
     const size_t lds = conv_lds<K>(PIPED) + (sizeof(PT) == 1 ? 768 * 4 : 0);                                              \
-    SRLZ_MAX_LDS((skinny_conv_kernel<K, PAD, BN, MU, PT>), lds);                                                          \
-    SRLZ_LAUNCH((skinny_conv_kernel<K, PAD, BN, MU, PT>), grid, block, lds, st, img, w, feat, stats, d->n, d->c,          \
+    SRLZ_MAX_LDS(KERNEL, lds);                                                                                            \
+    SRLZ_LAUNCH(KERNEL, grid, block, lds, st, img, w, feat, stats, d->n, d->c,                                            \
                 d->himg, d->wimg, d->hf, d->wf, ty, tx, y_raw, y_bnp, images_per_group(d), lut);                          \
   } while (0)
+#define SRLZ_CONV_LAUNCH(BN, MU, PIPED) SRLZ_CONV_LAUNCH_KERNEL((skinny_conv_kernel<K, PAD, BN, MU, PT>), PIPED)
   bool launched = false;
+  if constexpr (K == 7) if (!generic && buffer_staging_ok(d)) {
+    SRLZ_CONV_LAUNCH_KERNEL((skinny_conv_kernel<K, PAD, false, false, BufStaged<PT>>), true);
+    launched = true;
+  }
   if constexpr (K == 4 && sizeof(PT) == 4) if (y_raw) {
     if (multi) SRLZ_CONV_LAUNCH(true, true, false); else SRLZ_CONV_LAUNCH(true, false, false);
     launched = true;
@@ -864,6 +1050,7 @@ static int launch_conv(const PT* img, const float* w, float* feat, float* stats,
     if (multi) SRLZ_CONV_LAUNCH(false, true, true); else SRLZ_CONV_LAUNCH(false, false, true);
   }
 #undef SRLZ_CONV_LAUNCH
+#undef SRLZ_CONV_LAUNCH_KERNEL
   return 0;
 }
 
@@ -877,7 +1064,8 @@ static size_t wgrad_ws(const srlz_skinny_desc* d) {
 
 template <int K, int PAD, typename PT = float>
 static int launch_wgrad(const PT* img, const float* feat, float* dw, void* ws, size_t ws_bytes, const srlz_skinny_desc* d,
-                        hipStream_t st, const float* feat_bnp = nullptr, const PoolFuse* pfuse = nullptr, const float* lut = nullptr) {
+                        hipStream_t st, const float* feat_bnp = nullptr, const PoolFuse* pfuse = nullptr, const float* lut = nullptr,
+                        bool generic = false) {
   constexpr int NT = (Geo<K>::KT + 31) / 32;
   const int ty = (d->hf + 15) / 16, tx = (d->wf + 15) / 16;
   const int ntiles = d->n * ty * tx;
@@ -890,8 +1078,12 @@ static int launch_wgrad(const PT* img, const float* feat, float* dw, void* ws, s
   if (pfuse) pf = *pfuse;
   bool launched = false;
   if constexpr (K == 7) if (pf.y) {
-    SRLZ_LAUNCH((skinny_wgrad_kernel<K, PAD, true, PT>), dim3(g, d->c / 3), dim3(256), lds, st, img, feat, partial, d->n, d->c, d->himg,
-                d->wimg, d->hf, d->wf, ty, tx, feat_bnp, pf, images_per_group(d), lut);
+    if (!generic && buffer_staging_ok(d))
+      SRLZ_LAUNCH((skinny_wgrad_kernel<K, PAD, true, BufStaged<PT>>), dim3(g, d->c / 3), dim3(256), lds, st, img, feat, partial, d->n, d->c,
+                  d->himg, d->wimg, d->hf, d->wf, ty, tx, feat_bnp, pf, images_per_group(d), lut);
+    else
+      SRLZ_LAUNCH((skinny_wgrad_kernel<K, PAD, true, PT>), dim3(g, d->c / 3), dim3(256), lds, st, img, feat, partial, d->n, d->c, d->himg,
+                  d->wimg, d->hf, d->wf, ty, tx, feat_bnp, pf, images_per_group(d), lut);
     launched = true;
   }
   if (!launched)
@@ -917,20 +1109,45 @@ extern "C" int srlz_conv1_workgroups(const srlz_skinny_desc* d) {
   return persistent_grid(d->n * ((d->hf + 15) / 16) * ((d->wf + 15) / 16));
 }
 
-extern "C" int srlz_conv1_fwd(const float* x_nchw, const float* w_ref, float* y_nhwc, float* stats_partial,
-                              const srlz_skinny_desc* d, srlz_stream_t stream) {
+extern "C" int srlz_conv1_buffer_staging_supported(const srlz_skinny_desc* d) {
+  if (check_skinny(d)) return 0;
+  return buffer_staging_ok(d) ? 1 : 0;
+}
+
+static int conv1_fwd(const float* x_nchw, const float* w_ref, float* y_nhwc, float* stats_partial, const srlz_skinny_desc* d,
+                     srlz_stream_t stream, bool generic) {
   if (int rc = check_skinny(d)) return rc;
   SRLZ_REQUIRE(d->kind == 0, SRLZ_ERR_BAD_DESC, "conv1_fwd: descriptor kind must be 0");
   SRLZ_REQUIRE(x_nchw && w_ref && y_nhwc, SRLZ_ERR_NULL, "conv1_fwd: null pointer");
-  return launch_conv<7, 3>(x_nchw, w_ref, y_nhwc, stats_partial, d, as_stream(stream));
+  return launch_conv<7, 3>(x_nchw, w_ref, y_nhwc, stats_partial, d, as_stream(stream), nullptr, nullptr, nullptr, generic);
+}
+
+static int conv1_fwd_u8(const uint8_t* x_u8, const float* norm_lut, const float* w_ref, float* y_nhwc, float* stats_partial,
+                        const srlz_skinny_desc* d, srlz_stream_t stream, bool generic) {
+  if (int rc = check_skinny(d)) return rc;
+  SRLZ_REQUIRE(d->kind == 0, SRLZ_ERR_BAD_DESC, "conv1_fwd_u8: descriptor kind must be 0");
+  SRLZ_REQUIRE(x_u8 && norm_lut && w_ref && y_nhwc, SRLZ_ERR_NULL, "conv1_fwd_u8: null pointer");
+  return launch_conv<7, 3, uint8_t>(x_u8, w_ref, y_nhwc, stats_partial, d, as_stream(stream), nullptr, nullptr, norm_lut, generic);
+}
+
+extern "C" int srlz_conv1_fwd(const float* x_nchw, const float* w_ref, float* y_nhwc, float* stats_partial,
+                              const srlz_skinny_desc* d, srlz_stream_t stream) {
+  return conv1_fwd(x_nchw, w_ref, y_nhwc, stats_partial, d, stream, false);
 }
 
 extern "C" int srlz_conv1_fwd_u8(const uint8_t* x_u8, const float* norm_lut, const float* w_ref, float* y_nhwc,
                                  float* stats_partial, const srlz_skinny_desc* d, srlz_stream_t stream) {
-  if (int rc = check_skinny(d)) return rc;
-  SRLZ_REQUIRE(d->kind == 0, SRLZ_ERR_BAD_DESC, "conv1_fwd_u8: descriptor kind must be 0");
-  SRLZ_REQUIRE(x_u8 && norm_lut && w_ref && y_nhwc, SRLZ_ERR_NULL, "conv1_fwd_u8: null pointer");
-  return launch_conv<7, 3, uint8_t>(x_u8, w_ref, y_nhwc, stats_partial, d, as_stream(stream), nullptr, nullptr, norm_lut);
+  return conv1_fwd_u8(x_u8, norm_lut, w_ref, y_nhwc, stats_partial, d, stream, false);
+}
+
+extern "C" int srlz_debug_conv1_fwd_generic(const float* x_nchw, const float* w_ref, float* y_nhwc, float* stats_partial,
+                                            const srlz_skinny_desc* d, srlz_stream_t stream) {
+  return conv1_fwd(x_nchw, w_ref, y_nhwc, stats_partial, d, stream, true);
+}
+
+extern "C" int srlz_debug_conv1_fwd_u8_generic(const uint8_t* x_u8, const float* norm_lut, const float* w_ref, float* y_nhwc,
+                                               float* stats_partial, const srlz_skinny_desc* d, srlz_stream_t stream) {
+  return conv1_fwd_u8(x_u8, norm_lut, w_ref, y_nhwc, stats_partial, d, stream, true);
 }
 
 extern "C" size_t srlz_skinny_bwd_weight_workspace(const srlz_skinny_desc* d) {
@@ -964,7 +1181,7 @@ template <typename PT>
 static int conv1_bwd_weight_fused(const PT* x_nchw, const float* lut, const float* y_nhwc, const float* bnp, const uint8_t* argmax,
                                   const float* dpooled, const float* sums, int training, float* dw_ref, void* ws,
                                   size_t ws_bytes, const srlz_skinny_desc* d, const srlz_pool_desc* pd,
-                                  srlz_stream_t stream) {
+                                  srlz_stream_t stream, bool generic = false) {
   if (int rc = check_skinny(d)) return rc;
   SRLZ_REQUIRE(d->kind == 0 && pd, SRLZ_ERR_BAD_DESC, "conv1_bwd_weight_fused: descriptor kind must be 0");
   SRLZ_REQUIRE(x_nchw && y_nhwc && bnp && argmax && dpooled && sums && dw_ref && ws, SRLZ_ERR_NULL,
@@ -976,7 +1193,7 @@ static int conv1_bwd_weight_fused(const PT* x_nchw, const float* lut, const floa
   pf.y = y_nhwc; pf.argmax = argmax; pf.dpooled = dpooled; pf.bnp = bnp; pf.sums = sums;
   pf.HP = pd->hp; pf.WP = pd->wp; pf.pad = pd->pool_pad; pf.training = training;
   pf.inv_count = 1.0f / (float)((double)images_per_group(d) * d->hf * d->wf);  // BatchNorm count of ONE group
-  return launch_wgrad<7, 3, PT>(x_nchw, y_nhwc, dw_ref, ws, ws_bytes, d, as_stream(stream), nullptr, &pf, lut);
+  return launch_wgrad<7, 3, PT>(x_nchw, y_nhwc, dw_ref, ws, ws_bytes, d, as_stream(stream), nullptr, &pf, lut, generic);
 }
 
 extern "C" int srlz_conv1_bwd_weight_fused(const float* x_nchw, const float* y_nhwc, const float* bnp, const uint8_t* argmax,
@@ -994,6 +1211,24 @@ extern "C" int srlz_conv1_bwd_weight_fused_u8(const uint8_t* x_u8, const float* 
   SRLZ_REQUIRE(norm_lut, SRLZ_ERR_NULL, "conv1_bwd_weight_fused_u8: null normalisation table");
   return conv1_bwd_weight_fused<uint8_t>(x_u8, norm_lut, y_nhwc, bnp, argmax, dpooled, sums, training, dw_ref, ws, ws_bytes, d, pd,
                                          stream);
+}
+
+extern "C" int srlz_debug_conv1_bwd_weight_fused_generic(const float* x_nchw, const float* y_nhwc, const float* bnp,
+                                                         const uint8_t* argmax, const float* dpooled, const float* sums, int training,
+                                                         float* dw_ref, void* ws, size_t ws_bytes, const srlz_skinny_desc* d,
+                                                         const srlz_pool_desc* pd, srlz_stream_t stream) {
+  return conv1_bwd_weight_fused<float>(x_nchw, nullptr, y_nhwc, bnp, argmax, dpooled, sums, training, dw_ref, ws, ws_bytes, d, pd,
+                                       stream, true);
+}
+
+extern "C" int srlz_debug_conv1_bwd_weight_fused_u8_generic(const uint8_t* x_u8, const float* norm_lut, const float* y_nhwc,
+                                                            const float* bnp, const uint8_t* argmax, const float* dpooled,
+                                                            const float* sums, int training, float* dw_ref, void* ws, size_t ws_bytes,
+                                                            const srlz_skinny_desc* d, const srlz_pool_desc* pd,
+                                                            srlz_stream_t stream) {
+  SRLZ_REQUIRE(norm_lut, SRLZ_ERR_NULL, "debug_conv1_bwd_weight_fused_u8_generic: null normalisation table");
+  return conv1_bwd_weight_fused<uint8_t>(x_u8, norm_lut, y_nhwc, bnp, argmax, dpooled, sums, training, dw_ref, ws, ws_bytes, d, pd,
+                                         stream, true);
 }
 
 extern "C" int srlz_convT_out_bwd_data(const float* dy_nchw, const float* w_ref, float* dx_nhwc, const float* x_raw,

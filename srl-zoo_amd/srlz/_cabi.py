@@ -101,6 +101,11 @@ _PROTOS = {
     "srlz_conv64_bwd_weight_plan": (c_int, [_C64, c_int, c_int, POINTER(c_int)]),
     "srlz_conv64_bwd_fused_workgroups": (c_int, [_C64]),
     "srlz_conv1_workgroups": (c_int, [_SK]),
+    "srlz_conv1_buffer_staging_supported": (c_int, [_SK]),
+    "srlz_debug_conv1_fwd_generic": (c_int, [P, P, P, P, _SK, P]),
+    "srlz_debug_conv1_fwd_u8_generic": (c_int, [P, P, P, P, P, _SK, P]),
+    "srlz_debug_conv1_bwd_weight_fused_generic": (c_int, [P, P, P, P, P, P, c_int, P, P, c_size_t, _SK, _PD, P]),
+    "srlz_debug_conv1_bwd_weight_fused_u8_generic": (c_int, [P, P, P, P, P, P, P, c_int, P, P, c_size_t, _SK, _PD, P]),
     "srlz_convT_out_os_plan": (c_int, [_SK, c_int, POINTER(c_int)]),
     "srlz_conv64_debug_program": (c_int, [_C64, c_int, POINTER(c_int), c_int]),
     "srlz_linear_debug_route": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, c_int, c_size_t, POINTER(c_int)]),
@@ -258,7 +263,8 @@ _NOT_STATUS = {"srlz_version", "srlz_device_cus", "srlz_conv64_fwd_tiles", "srlz
                "srlz_conv64_wino_tiles", "srlz_conv64_wino_bwd_data_rows",
                "srlz_conv64_debug_program", "srlz_comm_world", "srlz_dense_supported",
                "srlz_dense_out_fwd_loss_workgroups", "srlz_reward_probe_chunk_rows", "srlz_infer_block_supported",
-               "srlz_infer_tile", "srlz_conv64_bwd_fused_workgroups", "srlz_conv1_workgroups"}
+               "srlz_infer_tile", "srlz_conv64_bwd_fused_workgroups", "srlz_conv1_workgroups",
+               "srlz_conv1_buffer_staging_supported"}
 
 EXPORTED = sorted(_PROTOS.keys())
 
