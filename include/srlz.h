@@ -888,6 +888,60 @@ int srlz_infer_block(const void* x, const float* norm_lut /* kind IN only */, co
                      const srlz_infer_block_desc* d, srlz_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Deployment decoder (csrc/infer_dec.hip): states to camera frames in six launches.  Replaces, per call of
+ *   srl_model.decode(state) in eval mode + deNormalize        evaluation/enjoy_latent.py:21-39; autoencoders.py:111-118; vae.py:68-75
+ * the decoder stack  ConvTranspose2d, BatchNorm2d, ReLU (x4), ConvTranspose2d      models/models.py:65-83
+ * each layer as ONE launch.  decoder_fc is the existing srlz_linear_fwd, whose [N,2304] output viewed [N,64,6,6] kind FIRST reads.
+ *   kind SRLZ_INFER_DEC_FIRST  3x3 stride 2, 64 -> 64, out = 2 in + 1   models/models.py:67-69   x: fp32 [N,64,hi,wi]
+ *   kind SRLZ_INFER_DEC_MID    3x3 stride 2, 64 -> 64, out = 2 in + 1   models/models.py:71-81   x: fp32 NHWC
+ *   kind SRLZ_INFER_DEC_OUT    4x4 stride 2, 64 -> c_out in {3, 6}, out = 2 in + 2   models/models.py:83   x: fp32 NHWC
+ * FIRST / MID (srlz_infer_dec_block):  out = relu((convT(x) + bias) * scale + shift), fp32 NHWC [N,2hi+1,2wi+1,64]; scale / shift =
+ * the record of srlz_bn_eval_params (floats [128,192) and [192,256)), applied with the expression of srlz_infer_block behind the bias.
+ * The raw ConvTranspose output is never written.
+ * OUT (srlz_infer_dec_out): out_u8 = 0 writes the reference's decode tensor, fp32 [N,c_out,ho,wo]; out_u8 = 1 writes the picture as
+ * BYTES addressed by four element strides, element (n, c, y, x) of that tensor at byte n*out_stride_n + c*out_stride_c +
+ * y*out_stride_y + x*out_stride_x:
+ *   v = clip(fadd(fmul(d, std[c % 3]), mean[c % 3]), 0, 1), byte = (uint8) rintf(fmul(v, 255)), NaN -> 0      preprocessing/utils.py:54-66
+ * (the arithmetic of srlz_decoded_to_sheet_u8).  The reference's planar [N,C,W,H] (strides C*ho*wo, ho*wo, wo, 1) and a camera's
+ * [N,H,W,C] frames (ho = W, wo = H; strides H*W*C, 1, C, W*C: byte (n,y,x,c) of a frame is decoded[n][c][x][y]) are the same kernel;
+ * bgr = 1 stores channel c of each camera (group of three) at 2 - c % 3.  The out strides are ignored for fp32 output.
+ * The input strides state the layout the kernel reads and must be the contiguous ones: [N,64,hi,wi] (64*hi*wi, hi*wi, wi, 1) for
+ * FIRST, NHWC (hi*wi*64, 1, wi*64, 64) for MID and OUT.  Weights: nn.ConvTranspose2d's [64, c_out, k, k].
+ * No atomics; every output's sum has one order that depends on neither n nor the tile boundaries: two runs are bit-identical, row i
+ * of a batch has the bits of state i decoded alone, and the bytes are exactly the expression above on the fp32 output.
+ * Rejected before any launch with SRLZ_ERR_BAD_DESC (srlz_infer_dec_supported says so first): an unknown kind, c_in != 64, c_out
+ * outside 64 / {3, 6}, an empty map, input strides other than the contiguous ones, output byte strides under which two elements share
+ * an address, out_u8 on a block kind, more than 2^31 - 1 tiles or a frame beyond 32-bit byte offsets.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define SRLZ_INFER_DEC_FIRST 0
+#define SRLZ_INFER_DEC_MID 1
+#define SRLZ_INFER_DEC_OUT 2
+typedef struct {
+  int n;          /* states */
+  int c_in;       /* 64 */
+  int c_out;      /* 64 (FIRST, MID), 3 or 6 (OUT) */
+  int hi, wi;     /* input map */
+  int kind;       /* SRLZ_INFER_DEC_* */
+  int out_u8;     /* OUT only: 1 = bytes by the out strides, 0 = fp32 [N,c_out,ho,wo] */
+  int bgr;        /* bytes only: 1 = reverse the three channels of each camera */
+  long long in_stride_n, in_stride_c, in_stride_y, in_stride_x;     /* input element strides (checked) */
+  long long out_stride_n, out_stride_c, out_stride_y, out_stride_x; /* byte output element strides */
+} srlz_infer_dec_desc;
+int srlz_infer_dec_supported(const srlz_infer_dec_desc* d);
+/* Size of the output map: 2 hi + 1 (FIRST, MID), 2 hi + 2 (OUT), the same for the widths; either pointer may be NULL.  Host only. */
+int srlz_infer_dec_out_dims(const srlz_infer_dec_desc* d, int* ho, int* wo);
+/* Edge of the square tile of CELLS one workgroup of that kind owns (a cell = one input position and the 2 x 2 outputs under it; the
+ * cell grid of an hi x wi map is (hi + 1) x (wi + 1)); 0 for an unknown kind.  Host only; tests size their multi-tile cases by it. */
+int srlz_infer_dec_tile(int kind);
+/* The kernels' private copy of a ConvTranspose2d weight [64, c_out, k, k]: floats it takes (0 outside the table), the packing launch. */
+long long srlz_infer_dec_packed_floats(int kind, int c_out);
+int srlz_infer_dec_pack_weights(const float* w_ref, float* wpack, int kind, int c_out, srlz_stream_t stream);
+int srlz_infer_dec_block(const float* x, const float* wpack, const float* bias /*[64]*/, const float* bnp, float* out,
+                         const srlz_infer_dec_desc* d, srlz_stream_t stream);
+int srlz_infer_dec_out(const float* x, const float* wpack, const float* bias /*[c_out]*/, void* out, const srlz_infer_dec_desc* d,
+                       srlz_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Debug / calibration hooks (not on the product path).
  * ------------------------------------------------------------------------------------------------------------ */
 /* Host-only: dump the virtual-grid program of a 64->64 convolution (tests interpret it on the CPU).

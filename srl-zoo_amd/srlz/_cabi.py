@@ -62,6 +62,17 @@ class InferBlockDesc(Structure):
 
 INFER_IN, INFER_MID, INFER_LAST = 0, 1, 2
 
+
+class InferDecDesc(Structure):
+    """srlz_infer_dec_desc; build with srlz.ops.infer_dec_desc()."""
+    _fields_ = [("n", c_int), ("c_in", c_int), ("c_out", c_int), ("hi", c_int), ("wi", c_int), ("kind", c_int), ("out_u8", c_int),
+                ("bgr", c_int), ("in_stride_n", c_longlong), ("in_stride_c", c_longlong), ("in_stride_y", c_longlong),
+                ("in_stride_x", c_longlong), ("out_stride_n", c_longlong), ("out_stride_c", c_longlong),
+                ("out_stride_y", c_longlong), ("out_stride_x", c_longlong)]
+
+
+INFER_DEC_FIRST, INFER_DEC_MID, INFER_DEC_OUT = 0, 1, 2
+
 P = c_void_p
 _BO = POINTER(BnBwdOperand)
 _C64 = POINTER(Conv64Desc)
@@ -69,6 +80,7 @@ _SK = POINTER(SkinnyDesc)
 _PD = POINTER(PoolDesc)
 _CN = POINTER(ConvNDesc)
 _IB = POINTER(InferBlockDesc)
+_ID = POINTER(InferDecDesc)
 
 # name -> (restype, argtypes); restype c_int functions are status-checked
 _PROTOS = {
@@ -252,6 +264,13 @@ _PROTOS = {
     "srlz_infer_packed_floats": (c_longlong, [c_int, c_int]),
     "srlz_infer_pack_weights": (c_int, [P, P, c_int, c_int, P]),
     "srlz_infer_block": (c_int, [P, P, P, P, P, _IB, P]),
+    "srlz_infer_dec_supported": (c_int, [_ID]),
+    "srlz_infer_dec_out_dims": (c_int, [_ID, POINTER(c_int), POINTER(c_int)]),
+    "srlz_infer_dec_tile": (c_int, [c_int]),
+    "srlz_infer_dec_packed_floats": (c_longlong, [c_int, c_int]),
+    "srlz_infer_dec_pack_weights": (c_int, [P, P, c_int, c_int, P]),
+    "srlz_infer_dec_block": (c_int, [P, P, P, P, P, _ID, P]),
+    "srlz_infer_dec_out": (c_int, [P, P, P, P, _ID, P]),
 }
 
 # entry points whose int return value is data, not a status
@@ -264,7 +283,7 @@ _NOT_STATUS = {"srlz_version", "srlz_device_cus", "srlz_conv64_fwd_tiles", "srlz
                "srlz_conv64_debug_program", "srlz_comm_world", "srlz_dense_supported",
                "srlz_dense_out_fwd_loss_workgroups", "srlz_reward_probe_chunk_rows", "srlz_infer_block_supported",
                "srlz_infer_tile", "srlz_conv64_bwd_fused_workgroups", "srlz_conv1_workgroups",
-               "srlz_conv1_buffer_staging_supported"}
+               "srlz_conv1_buffer_staging_supported", "srlz_infer_dec_supported", "srlz_infer_dec_tile"}
 
 EXPORTED = sorted(_PROTOS.keys())
 

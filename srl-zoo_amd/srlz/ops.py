@@ -2154,3 +2154,65 @@ def infer_block(x, wpack, bnp, out, d, lut=None):
     normalisation table) or fp32 NHWC; `out` must hold n * 64 * hp * wp floats."""
     C.infer_block(ptr(x), ptr(lut), ptr(wpack), ptr(bnp), ptr(out), ctypes.byref(d), stream())
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# Deployment decoder (csrc/infer_dec.hip): one eval-mode decoder layer per launch — models/models.py:65-83.  Blocks: ConvTranspose 3x3
+# s2 + bias + BatchNorm affine + ReLU; out: ConvTranspose 4x4 s2 + bias to the decode tensor or to the picture's bytes.
+# Thin: the caller (srlz/deploy.py) owns every buffer; nothing is allocated here, and no autograd node is made.
+# ----------------------------------------------------------------------------------------------------------------
+INFER_DEC_FIRST, INFER_DEC_MID, INFER_DEC_OUT = C.INFER_DEC_FIRST, C.INFER_DEC_MID, C.INFER_DEC_OUT
+
+
+def infer_dec_desc(kind, n, hi, wi, c_out=None, out_u8=False, bgr=False, in_strides=None, out_strides=None, c_in=64):
+    """srlz_infer_dec_desc of `n` maps [64, hi, wi].  c_out defaults to 64 (FIRST, MID) / 3 (OUT).  in_strides: element strides
+    (n, c, y, x) of the input, None = the contiguous ones of that kind ([N,64,hi,wi] for FIRST, NHWC otherwise).  out_strides: byte
+    output only, element strides (n, c, y, x) of the decode tensor [N,c_out,ho,wo] in the picture; None = the reference's planar
+    [N,C,W,H] bytes."""
+    if c_out is None:
+        c_out = 3 if kind == INFER_DEC_OUT else 64
+    if in_strides is None:
+        in_strides = (64 * hi * wi, hi * wi, wi, 1) if kind == INFER_DEC_FIRST else (hi * wi * 64, 1, wi * 64, 64)
+    if out_strides is None:
+        ho, wo = (2 * hi + 2, 2 * wi + 2) if kind == INFER_DEC_OUT else (2 * hi + 1, 2 * wi + 1)
+        out_strides = (c_out * ho * wo, ho * wo, wo, 1)
+    return C.InferDecDesc(n, c_in, c_out, hi, wi, kind, 1 if out_u8 else 0, 1 if bgr else 0, *[int(s) for s in tuple(in_strides) + tuple(out_strides)])
+
+
+def infer_dec_supported(d):
+    return bool(C.infer_dec_supported(ctypes.byref(d)))
+
+
+def infer_dec_out_dims(d):
+    """(ho, wo) of a supported descriptor; SrlzError for a rejected one."""
+    v = [ctypes.c_int(0) for _ in range(2)]
+    C.infer_dec_out_dims(ctypes.byref(d), *[ctypes.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def infer_dec_pack(weight, kind, out=None):
+    """The kernels' copy of a ConvTranspose2d weight [64, c_out, k, k] (written into `out` when given: a refresh allocates nothing)."""
+    weight = _check(weight.detach(), "infer_dec_pack weight")
+    c_out = weight.shape[1] if weight.dim() == 4 else -1
+    nfl = C.infer_dec_packed_floats(kind, c_out)
+    k = 4 if kind == INFER_DEC_OUT else 3
+    if nfl <= 0 or tuple(weight.shape) != (64, c_out, k, k):
+        raise C.SrlzError("infer_dec_pack: no layer of kind %d takes a weight of shape %s" % (kind, tuple(weight.shape)))
+    if out is None:
+        out = torch.empty(nfl, dtype=torch.float32, device=weight.device)
+    elif out.numel() != nfl or out.dtype != torch.float32 or not out.is_contiguous():
+        raise C.SrlzError("infer_dec_pack: `out` must be %d contiguous float32 values" % nfl)
+    C.infer_dec_pack_weights(ptr(weight), ptr(out), kind, c_out, stream())
+    return out
+
+
+def infer_dec_block(x, wpack, bias, bnp, out, d):
+    """One launch: out = relu((convT3x3s2(x) + bias) * scale + shift), fp32 NHWC; `out` must hold n * (2hi+1) * (2wi+1) * 64 floats."""
+    C.infer_dec_block(ptr(x), ptr(wpack), ptr(bias), ptr(bnp), ptr(out), ctypes.byref(d), stream())
+    return out
+
+
+def infer_dec_out(x, wpack, bias, out, d):
+    """One launch: convT4x4s2(x) + bias as fp32 [n,c_out,ho,wo], or (d.out_u8) as the picture's bytes by d's out strides."""
+    C.infer_dec_out(ptr(x), ptr(wpack), ptr(bias), ptr(out), ctypes.byref(d), stream())
+    return out
