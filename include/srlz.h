@@ -942,6 +942,42 @@ int srlz_infer_dec_out(const float* x, const float* wpack, const float* bias /*[
                        srlz_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Deployment dynamics (csrc/rollout.hip): states and plans to final states and returns in ONE launch.  Replaces, per step of a
+ * controller that scores candidate action sequences on the learned state,
+ *   forwardModel: state + forward_net(cat(state, onehot(action)))          models/forward_inverse.py:21-31
+ *   rewardModel:  reward_net(cat(state, next_state)), Linear-ReLU-Linear-ReLU-Linear   models/forward_inverse.py:78-95
+ * (six launches of the training kernels a step).  R = N * K independent rows (environment n, candidate plan k), T sequential steps;
+ * per row, s_0 = states[n], a_t = plans[n][k][t]:
+ *   d_t     = fl(fl(Wf[:, :S] . s_t + Wf[:, S + a_t]) + bf)       the one-hot selects a column, it is never materialised
+ *   s_{t+1} = fl(s_t + d_t)                                        the residual add rounded separately, as srlz_linear_fwd_res does
+ *   l_t     = W3 . relu(W2 . relu(W1 . [s_t ; s_{t+1}] + b1) + b2) + b3
+ *   ret    += fl(g_t * softmax(l_t)[1]);  g_0 = 1, g_{t+1} = fl(g_t * gamma);  softmax(l)[1] = 1 / (1 + exp(l[0] - l[1]))
+ * states fp32 [N,S]; plans int32 [N,K,T] (plan_env_stride = K * T) or one [K,T] shared by every environment (plan_env_stride = 0,
+ * nothing is copied); the weights in the reference's own layouts, read in place at every call: forward_net.weight wf [S,S+A], bias bf
+ * [S], reward_net.0/2/4 w1 [H,2S], b1 [H], w2 [H,H], b2 [H], w3 [2,H], b3 [2].  The six reward-head pointers are all given or all
+ * NULL; NULL means no reward work, and then returns and reward_logits must be NULL too (and H, n_rewards are not looked at).
+ * Outputs, each optional (NULL) except the first: final_states [N,K,S] = s_T; returns [N,K]; trajectory [N,K,T,S], entry t = s_{t+1};
+ * reward_logits [N,K,T,2].
+ * fp32 throughout, the contractions over S on v_mfma_f32_32x32x2_f32; a tile of 32 rows stays in LDS from step 0 to step T-1.  No
+ * atomics, and every sum's order depends on (S, A, H) alone: two runs are bit-identical; a call of T steps leaves the bits of T calls
+ * of one step each fed the previous call's final_states (trajectory, reward_logits); a row's outputs do not depend on the other rows
+ * of the call or on its place in it; shared plans give the bits of the same plans tiled.
+ * An action outside [0, A) is never read through: from that step on the row's states, logits and return are NaN; its earlier steps
+ * and every other row are untouched.
+ * Limits (srlz_rollout_supported; the state tile, the partial blocks of layer 1 and the small operands take 115 KB of the 160 KB of
+ * LDS at the limits, the forward model's accumulators 32 registers a wave): 1 <= S <= 512, 1 <= A <= 65536, 1 <= H <= 32,
+ * n_rewards == 2.  Outside them, N, K or T < 1, N * K above 2^31 - 33, a plan stride other than 0 or K * T, a partly given reward
+ * head or reward outputs without one: SRLZ_ERR_BAD_DESC before any launch, nothing written; a missing required pointer SRLZ_ERR_NULL.
+ * ------------------------------------------------------------------------------------------------------------ */
+int srlz_rollout_supported(int S, int A, int H, int n_rewards);
+/* Rows one workgroup owns (host only; tests size their multi-tile cases by it). */
+int srlz_rollout_tile(void);
+int srlz_rollout(const float* states, const int* plans, long long plan_env_stride, const float* wf, const float* bf,
+                 const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
+                 float* final_states, float* returns, float* trajectory, float* reward_logits, int N, int K, int T, int S, int A,
+                 int H, int n_rewards, float gamma, srlz_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Debug / calibration hooks (not on the product path).
  * ------------------------------------------------------------------------------------------------------------ */
 /* Host-only: dump the virtual-grid program of a 64->64 convolution (tests interpret it on the CPU).

@@ -271,6 +271,10 @@ _PROTOS = {
     "srlz_infer_dec_pack_weights": (c_int, [P, P, c_int, c_int, P]),
     "srlz_infer_dec_block": (c_int, [P, P, P, P, P, _ID, P]),
     "srlz_infer_dec_out": (c_int, [P, P, P, P, _ID, P]),
+    "srlz_rollout_supported": (c_int, [c_int, c_int, c_int, c_int]),
+    "srlz_rollout_tile": (c_int, []),
+    "srlz_rollout": (c_int, [P, P, c_longlong, P, P, P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                             c_float, P]),
 }
 
 # entry points whose int return value is data, not a status
@@ -283,7 +287,8 @@ _NOT_STATUS = {"srlz_version", "srlz_device_cus", "srlz_conv64_fwd_tiles", "srlz
                "srlz_conv64_debug_program", "srlz_comm_world", "srlz_dense_supported",
                "srlz_dense_out_fwd_loss_workgroups", "srlz_reward_probe_chunk_rows", "srlz_infer_block_supported",
                "srlz_infer_tile", "srlz_conv64_bwd_fused_workgroups", "srlz_conv1_workgroups",
-               "srlz_conv1_buffer_staging_supported", "srlz_infer_dec_supported", "srlz_infer_dec_tile"}
+               "srlz_conv1_buffer_staging_supported", "srlz_infer_dec_supported", "srlz_infer_dec_tile", "srlz_rollout_supported",
+               "srlz_rollout_tile"}
 
 EXPORTED = sorted(_PROTOS.keys())
 

@@ -24,7 +24,8 @@ model's mode or torch's RNG, and runs on the current stream.  The states it retu
 overwritten by the next call (clone them to keep them), and one encoder serves one stream at a time.
 
 The way back — FrameDecoder, states to camera frames in six launches, and reconstruct(encoder, decoder, frames) — is the second half
-of this file.
+of this file; LatentDynamics — states and plans through the forward and reward heads to returns in one launch — and imagine are the
+third part.
 """
 import numpy as np
 import torch
@@ -537,3 +538,351 @@ def reconstruct(encoder, decoder, frames):
     """decoder(encoder(frames)): camera frames through the state and back with no host round trip — the decoder reads the encoder's
     state buffer in place.  Bit-identical to the two calls made separately."""
     return decoder(encoder(frames))
+
+
+# =============================================================================================================
+# Deployment dynamics: states and plans to final states and returns in one launch.
+#
+#     dyn = LatentDynamics(model, max_rows=8192, max_horizon=32)   # SRLModules / SRLModulesSplit / a learner
+#     dyn = LatentDynamics.from_log_folder("logs/<dataset>/<experiment>/")
+#     dyn.heads                      # subset of ("forward", "inverse", "reward") the model's losses trained
+#     dyn.route                      # "rollout" or "model", as StateEncoder.route
+#     nxt = dyn.step(states, actions)              # [N,S], [N] -> [N,S]: the same kernel with K = T = 1
+#     out = dyn.rollout(states, plans, gamma=1.0, keep_trajectory=False, keep_logits=False)
+#     out.final_states, out.returns, out.trajectory, out.reward_logits, out.best   # [N,K,S], [N,K], [N,K,T,S], [N,K,T,2], [N]
+#     a = dyn.act(states, plans)                   # first action of each environment's best plan, [N] int64, no host synchronisation
+#     dyn.reward_logits(states, next_states); dyn.action_logits(states, next_states)   # the model's own heads under no_grad
+#     frames = imagine(dyn, decoder, states, plans)   # the trajectories through a FrameDecoder
+#
+# What sits between StateEncoder and FrameDecoder: the three heads every srl_model.pth carries (models/forward_inverse.py).  A
+# controller on the learned state scores K candidate action sequences per environment by rolling each through forwardModel and asking
+# rewardModel at every step.  A rollout IS that composition of the owner's own methods under no_grad:
+#     s' = owner.forwardModel(s, a_t);  l_t = owner.rewardModel(s, s');  ret += g * softmax(l_t)[1];  g *= gamma;  s = s'
+# which through the training kernels is six launches and six temporaries a step.  Route "rollout" runs all N * K rows and all T steps
+# as ONE launch of csrc/rollout.hip, the state tile on chip throughout, the weights read in place from the model's own parameters (no
+# refresh(): further training is seen by the next call).  It serves SRLModules of every model_type — the heads do not depend on the
+# encoder.  Route "model" computes the composition above step by step: SRLModulesSplit (whose heads see masked states), head shapes
+# srlz_rollout_supported refuses, and calls of more than max_rows rows or max_horizon steps.  Nothing is rejected for size, nothing is
+# approximated.
+#
+# plans: integers [N,K,T], or [K,T] shared by every environment (read with a stride of 0, never tiled), or one bare [T]; states [N,S] or
+# one bare [S]; numpy or device tensors.  Outputs drop the axes the inputs did not have.  Host plans are range-checked here; on the
+# device an action outside [0, A) turns its row NaN from that step on (include/srlz.h).  returns, reward_logits and best need the
+# reward head and are None without it; best = argmax_k returns, ties to the lowest k, NaN returns never chosen over a number.
+# Using a head the model's losses did not train raises ValueError; untrained_ok=True overrides it.  A module without .losses allows all.
+#
+# A "rollout" call launches on the current stream into buffers made at construction (states, plans, final states, returns, and the
+# trajectory / logits buffers of max_rows * max_horizon steps), builds no graph, and leaves modes, parameters and torch's RNG alone.
+# What it returns are views of those buffers, valid until the next call.
+# =============================================================================================================
+ROUTE_ROLLOUT = "rollout"
+HEADS = ("forward", "inverse", "reward")
+
+
+class Rollout(object):
+    """What LatentDynamics.rollout returns; a field the call did not ask for (or has no head for) is None."""
+    __slots__ = ("final_states", "returns", "trajectory", "reward_logits", "best")
+
+    def __init__(self, final_states, returns=None, trajectory=None, reward_logits=None, best=None):
+        self.final_states, self.returns, self.trajectory, self.reward_logits, self.best = final_states, returns, trajectory, reward_logits, best
+
+
+def _dynamics_owner(model):
+    """The module that owns forward_net / inverse_net / reward_net (a learner's .model, or the module itself)."""
+    owner, _ = _core(model)
+    if getattr(owner, "forward_net", None) is None:
+        raise ValueError("%s carries no forward / inverse / reward heads: LatentDynamics needs SRLModules or SRLModulesSplit"
+                         % type(owner).__name__)
+    return owner
+
+
+def trained_heads(model):
+    """The subset of ("forward", "inverse", "reward") the model's losses trained; all three for a module without .losses."""
+    owner = _dynamics_owner(model)
+    losses = getattr(owner, "losses", None)
+    return HEADS if losses is None else tuple(h for h in HEADS if h in losses)
+
+
+def check_head(model, head, untrained_ok=False):
+    """ValueError when `head` was not trained by the model's losses (unless untrained_ok)."""
+    if untrained_ok or head in trained_heads(model):
+        return
+    raise ValueError("the %s head of this model was never trained: its losses are %s (untrained_ok=True uses the head as it is)"
+                     % (head, list(getattr(_dynamics_owner(model), "losses", []))))
+
+
+def dynamics_dims(model):
+    """(S, A, H, n_rewards) of the model's heads; H = n_rewards = 0 when reward_net is not the reference's three-layer head."""
+    owner = _dynamics_owner(model)
+    fw = owner.forward_net
+    s, a = fw.out_features, fw.in_features - fw.out_features
+    rn = owner.reward_net
+    three = isinstance(rn, torch.nn.Sequential) and len(rn) == 5 and all(isinstance(rn[i], torch.nn.Linear) for i in (0, 2, 4))
+    if not three or rn[0].in_features != 2 * s or rn[2].in_features != rn[0].out_features or rn[2].out_features != rn[0].out_features \
+            or rn[4].in_features != rn[0].out_features or any(rn[i].bias is None for i in (0, 2, 4)) or fw.bias is None:
+        return s, a, 0, 0
+    return s, a, rn[0].out_features, rn[4].out_features
+
+
+def dynamics_route_for(model):
+    """The route a LatentDynamics of `model` takes for calls within max_rows and max_horizon (host only: no GPU is asked for)."""
+    from models.modules import SRLModules
+    owner = _dynamics_owner(model)
+    s, a, h, nr = dynamics_dims(model)
+    return ROUTE_ROLLOUT if isinstance(owner, SRLModules) and a >= 1 and ops.rollout_supported(s, a, h, nr) else ROUTE_MODEL
+
+
+def check_plans(plans, n, n_actions):
+    """Validate a call's plans: integers, [N,K,T] with N = n, or [K,T], or one bare [T]; host plans within [0, n_actions).
+    Returns (k, t, shared, bare): plans per environment, steps, whether one [K,T] serves every environment, whether one bare plan came."""
+    if not isinstance(plans, (np.ndarray, torch.Tensor)):
+        raise ValueError("plans must be a numpy array or a torch tensor, got %s" % type(plans).__name__)
+    is_int = np.issubdtype(plans.dtype, np.integer) if isinstance(plans, np.ndarray) else \
+        plans.dtype in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)
+    if not is_int:
+        raise ValueError("plans must be integer actions (got %s)" % (plans.dtype,))
+    shape = tuple(plans.shape)
+    if len(shape) not in (1, 2, 3):
+        raise ValueError("plans must be [N,K,T], [K,T] or [T], got shape %s" % (shape,))
+    if len(shape) == 3 and shape[0] != n:
+        raise ValueError("plans of shape %s are for %d environments, the call has %d states" % (shape, shape[0], n))
+    if min(shape) < 1:
+        raise ValueError("plans of shape %s hold no action" % (shape,))
+    if isinstance(plans, np.ndarray) or plans.device.type == "cpu":
+        lo, hi = int(plans.min()), int(plans.max())
+        if lo < 0 or hi >= n_actions:
+            raise ValueError("plans must hold actions in [0, %d), got %d .. %d" % (n_actions, lo, hi))
+    return (shape[-2] if len(shape) > 1 else 1), shape[-1], len(shape) < 3, len(shape) == 1
+
+
+class LatentDynamics(object):
+    def __init__(self, model, max_rows=8192, max_horizon=32, untrained_ok=False, route=None):
+        """model: SRLModules / SRLModulesSplit / a learner.  max_rows: N * K rows a "rollout" call may take, max_horizon: its steps;
+        beyond either a call takes route "model".  untrained_ok: use heads the model's losses did not train (seeded tests).
+        route="model" forces the fallback for every call (tools/kb_dynamics.py measures the two routes side by side)."""
+        if route not in (None, ROUTE_MODEL):
+            raise ValueError("route must be None or 'model', got %r" % (route,))
+        if int(max_rows) < 1 or int(max_horizon) < 1:
+            raise ValueError("max_rows and max_horizon must be at least 1, got %r and %r" % (max_rows, max_horizon))
+        self.owner = _dynamics_owner(model)  # (ValueError for a model without heads, before anything touches a GPU)
+        self.heads = trained_heads(model)
+        self.untrained_ok = bool(untrained_ok)
+        self.state_dim, self.n_actions, self._h, self._nr = dynamics_dims(model)
+        picked = dynamics_route_for(model) if route is None else ROUTE_MODEL
+        from models.learner import _requireGpu
+        _requireGpu(True)
+        self.max_rows, self.max_horizon = int(max_rows), int(max_horizon)
+        self._route, self.last_route = picked, None
+        self.device = next(self.owner.forward_net.parameters()).device
+        if self.device.type != "cuda":
+            raise C.SrlzError("LatentDynamics: the model must live on the GPU (there is no CPU path)")
+        if self._route != ROUTE_ROLLOUT:
+            return
+        r, t, s, dev = self.max_rows, self.max_horizon, self.state_dim, self.device
+        self._states = torch.empty((r, s), dtype=torch.float32, device=dev)
+        self._pin_states = torch.empty((r, s), dtype=torch.float32).pin_memory()
+        self._plans = torch.empty(r * t, dtype=torch.int32, device=dev)
+        self._pin_plans = torch.empty(r * t, dtype=torch.int32).pin_memory()
+        self._final = torch.empty(r * s, dtype=torch.float32, device=dev)
+        self._returns = torch.empty(r, dtype=torch.float32, device=dev)
+        self._traj = torch.empty(r * t * s, dtype=torch.float32, device=dev)
+        self._logits = torch.empty(r * t * 2, dtype=torch.float32, device=dev)
+
+    @classmethod
+    def from_log_folder(cls, log_folder, max_rows=8192, max_horizon=32, valid_models=None):
+        """The dynamics of a trained experiment: <log_folder>/exp_config.json + srl_model.pth (SRL4robotics.loadSavedModel)."""
+        from models.learner import SRL4robotics, _requireGpu
+        _requireGpu(True)
+        if valid_models is None:
+            valid_models = ["forward", "inverse", "reward", "priors", "episode-prior", "reward-prior", "triplet", "autoencoder", "vae",
+                            "perceptual", "dae", "random"]
+        if not log_folder.endswith("/"):
+            log_folder += "/"
+        srl, _ = SRL4robotics.loadSavedModel(log_folder, valid_models, cuda=True)
+        srl.model.eval()
+        return cls(srl.model, max_rows=max_rows, max_horizon=max_horizon)
+
+    @property
+    def route(self):
+        """The route of the most recent call; before any call, the route that calls within max_rows and max_horizon take."""
+        return self.last_route or self._route
+
+    def _need(self, head):
+        check_head(self.owner, head, self.untrained_ok)
+
+    def _uses_reward(self):
+        return self.untrained_ok or "reward" in self.heads
+
+    # ---------------------------------------------------------------------------------------------------------
+    def _device_states(self, states, n, single, staged):
+        """The call's states as a contiguous fp32 device tensor [n, S]: the caller's own when it already is one, else (staged) a copy
+        into the staging buffer (host states travel through the pinned one), else a fresh tensor."""
+        if isinstance(states, np.ndarray):
+            states = torch.from_numpy(np.ascontiguousarray(states))
+        states = states.detach()
+        if single:
+            states = states.unsqueeze(0)
+        if states.device.type == "cuda" and states.is_contiguous() and states.dtype == torch.float32:
+            return states
+        if not staged:
+            return states.to(self.device, torch.float32).contiguous()
+        if states.device.type == "cuda":
+            self._states[:n].copy_(states)
+        else:
+            self._pin_states[:n].copy_(states)
+            self._states[:n].copy_(self._pin_states[:n], non_blocking=True)
+        return self._states[:n]
+
+    def _device_plans(self, plans, shape, staged):
+        """The call's plans on the device with `shape` ([N,K,T] or [K,T]): int32 in the staging buffer (staged), else int64."""
+        if isinstance(plans, np.ndarray):
+            plans = torch.from_numpy(np.ascontiguousarray(plans))
+        plans = plans.reshape(shape)
+        if not staged:
+            return plans.to(self.device, torch.int64).contiguous()
+        if plans.device.type == "cuda" and plans.dtype == torch.int32 and plans.is_contiguous():
+            return plans
+        numel = plans.numel()
+        dst = self._plans[:numel].view(shape)
+        if plans.device.type == "cuda":
+            dst.copy_(plans)
+        else:
+            pin = self._pin_plans[:numel].view(shape)
+            pin.copy_(plans)
+            dst.copy_(pin, non_blocking=True)
+        return dst
+
+    def _model_rollout(self, states, plans, gamma, reward, keep_trajectory, keep_logits):
+        """Route "model": the owner's own forwardModel and rewardModel, step by step, under no_grad.  states [n,S] fp32, plans int64
+        [n,k,t] or [k,t] on the device."""
+        n, s = states.shape
+        if plans.dim() == 2:
+            plans = plans.unsqueeze(0).expand(n, -1, -1)
+        k, t = plans.shape[1], plans.shape[2]
+        acts = plans.reshape(n * k, t)
+        traj, logits = [], []
+        with torch.no_grad():
+            cur = states.unsqueeze(1).expand(n, k, s).reshape(n * k, s).contiguous()
+            ret = torch.zeros(n * k, dtype=torch.float32, device=states.device) if reward else None
+            g = torch.ones((), dtype=torch.float32, device=states.device)
+            for step in range(t):
+                nxt = self.owner.forwardModel(cur, acts[:, step].contiguous())
+                if keep_trajectory:
+                    traj.append(nxt)
+                if reward:
+                    lg = self.owner.rewardModel(cur, nxt)
+                    if keep_logits:
+                        logits.append(lg)
+                    ret = ret + g * torch.softmax(lg, dim=1)[:, 1]
+                    g = g * gamma
+                cur = nxt
+        return (cur.view(n, k, s), ret.view(n, k) if reward else None,
+                torch.stack(traj, dim=1).view(n, k, t, s) if keep_trajectory else None,
+                torch.stack(logits, dim=1).view(n, k, t, 2) if keep_logits else None)
+
+    def _run(self, states, plans, gamma, reward, keep_trajectory, keep_logits):
+        """Both routes on checked inputs -> (final [n,k,S], returns [n,k] | None, trajectory | None, logits | None, plans on the device,
+        single, bare)."""
+        n, single = check_states(states, self.state_dim)
+        k, t, shared, bare = check_plans(plans, n, self.n_actions)
+        shape = (k, t) if shared else (n, k, t)
+        staged = self._route == ROUTE_ROLLOUT and n * k <= self.max_rows and t <= self.max_horizon
+        self.last_route = ROUTE_ROLLOUT if staged else ROUTE_MODEL
+        x = self._device_states(states, n, single, staged)
+        pl = self._device_plans(plans, shape, staged)
+        if not staged:
+            return self._model_rollout(x, pl, gamma, reward, keep_trajectory, keep_logits) + (pl, single, bare)
+        s, o = self.state_dim, self.owner
+        final = self._final[:n * k * s].view(n, k, s)
+        returns = self._returns[:n * k].view(n, k) if reward else None
+        traj = self._traj[:n * k * t * s].view(n, k, t, s) if keep_trajectory else None
+        logits = self._logits[:n * k * t * 2].view(n, k, t, 2) if keep_logits else None
+        rn = o.reward_net
+        head = (rn[0].weight, rn[0].bias, rn[2].weight, rn[2].bias, rn[4].weight, rn[4].bias) if reward else None
+        ops.rollout(x, pl, o.forward_net.weight, o.forward_net.bias, reward=head, final=final, returns=returns, trajectory=traj,
+                    reward_logits=logits, gamma=gamma)
+        return final, returns, traj, logits, pl, single, bare
+
+    @staticmethod
+    def _best(returns):
+        """argmax_k of returns [n,k], ties to the lowest k (torch.argmax returns the first maximal value); a NaN return is never
+        chosen over a number."""
+        return torch.nan_to_num(returns, nan=float("-inf")).argmax(dim=1)
+
+    @staticmethod
+    def _drop(x, single, bare, k_axis=1):
+        """Drop the axes the inputs did not have: K (a bare [T] plan) first, then N (a bare [S] state)."""
+        if x is None:
+            return None
+        if bare and x.dim() > k_axis:
+            x = x.squeeze(k_axis)
+        return x[0] if single else x
+
+    def rollout(self, states, plans, gamma=1.0, keep_trajectory=False, keep_logits=False):
+        self._need("forward")
+        reward = self._uses_reward()
+        if keep_logits and not reward:
+            self._need("reward")
+        final, returns, traj, logits, _, single, bare = self._run(states, plans, float(gamma), reward, keep_trajectory, keep_logits)
+        best = self._best(returns) if reward else None
+        d = self._drop
+        return Rollout(d(final, single, bare), d(returns, single, bare), d(traj, single, bare), d(logits, single, bare),
+                       best[0] if best is not None and single else best)
+
+    def step(self, states, actions):
+        """[N,S], [N] -> [N,S] (one bare state and one action: [S]): forwardModel alone, the same kernel with K = T = 1."""
+        self._need("forward")
+        n, single = check_states(states, self.state_dim)
+        if not isinstance(actions, (np.ndarray, torch.Tensor)):
+            actions = np.asarray(actions)
+        if tuple(actions.shape) != (() if single else (n,)):
+            raise ValueError("actions of shape %s do not match %d states" % (tuple(actions.shape), n))
+        final = self._run(states, actions.reshape(n, 1, 1), 1.0, False, False, False)[0]
+        return final[0, 0] if single else final[:, 0]
+
+    def act(self, states, plans):
+        """First action of each environment's best plan: [N] int64 ([] for one bare state), computed on the device."""
+        self._need("forward")
+        self._need("reward")
+        _, returns, _, _, pl, single, _ = self._run(states, plans, 1.0, True, False, False)
+        best = self._best(returns)
+        first = pl[..., 0].to(torch.int64)  # [n,k] or (shared) [k]
+        a = first[best] if first.dim() == 1 else first.gather(1, best.unsqueeze(1)).squeeze(1)
+        return a[0] if single else a
+
+    def _pair(self, states, next_states):
+        n, single = check_states(states, self.state_dim)
+        if check_states(next_states, self.state_dim) != (n, single):
+            raise ValueError("states and next_states must have the same shape")
+        return self._device_states(states, n, single, False), self._device_states(next_states, n, single, False), single
+
+    def reward_logits(self, states, next_states):
+        """The model's own rewardModel under no_grad: [N,2] ([2] for bare states)."""
+        self._need("reward")
+        a, b, single = self._pair(states, next_states)
+        with torch.no_grad():
+            out = self.owner.rewardModel(a, b)
+        return out[0] if single else out
+
+    def action_logits(self, states, next_states):
+        """The model's own inverseModel under no_grad: [N,A] ([A] for bare states)."""
+        self._need("inverse")
+        a, b, single = self._pair(states, next_states)
+        with torch.no_grad():
+            out = self.owner.inverseModel(a, b)
+        return out[0] if single else out
+
+
+def imagine(dynamics, decoder, states, plans):
+    """The imagined camera frames of every plan: the rollout's trajectory through a FrameDecoder, chunked by its max_batch so that
+    every chunk takes its "blocks" route.  uint8 [N,K,T] + the decoder's frame shape (axes the inputs did not have are dropped);
+    bit-identical to decoder(trajectory rows)."""
+    traj = dynamics.rollout(states, plans, keep_trajectory=True).trajectory
+    rows = traj.reshape(-1, traj.shape[-1])
+    frames, m = None, decoder.max_batch
+    for lo in range(0, rows.shape[0], m):
+        part = decoder(rows[lo:lo + m])
+        if frames is None:
+            frames = torch.empty((rows.shape[0],) + tuple(part.shape[1:]), dtype=part.dtype, device=part.device)
+        frames[lo:lo + part.shape[0]].copy_(part)
+    return frames.view(tuple(traj.shape[:-1]) + tuple(frames.shape[1:]))

@@ -2216,3 +2216,72 @@ def infer_dec_out(x, wpack, bias, out, d):
     """One launch: convT4x4s2(x) + bias as fp32 [n,c_out,ho,wo], or (d.out_u8) as the picture's bytes by d's out strides."""
     C.infer_dec_out(ptr(x), ptr(wpack), ptr(bias), ptr(out), ctypes.byref(d), stream())
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# Deployment dynamics (csrc/rollout.hip): R = N * K rows rolled T steps through forwardModel and rewardModel in one launch —
+# models/forward_inverse.py:21-31, 78-95.  Thin: the caller (srlz/deploy.py) owns every buffer; nothing is allocated here beyond the
+# upload of host plans, and no autograd node is made.
+# ----------------------------------------------------------------------------------------------------------------
+def rollout_supported(s, a, h=16, n_rewards=2):
+    return bool(C.rollout_supported(int(s), int(a), int(h), int(n_rewards)))
+
+
+def _rollout_f32(t, name, shape=None):
+    if t is None:
+        return None
+    if not torch.is_tensor(t) or t.device.type != "cuda" or t.dtype != torch.float32 or not t.is_contiguous():
+        raise C.SrlzError("rollout: %s must be a contiguous float32 device tensor" % name)
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise C.SrlzError("rollout: %s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
+    return t.detach()
+
+
+def rollout_plans(plans, n_actions, device):
+    """A call's plans as a contiguous int32 device tensor.  Host plans (numpy, lists, CPU tensors) are range-checked against
+    [0, n_actions) here and uploaded; device plans rely on the kernel's NaN rule (include/srlz.h) and are only converted to int32."""
+    if not torch.is_tensor(plans) or plans.device.type == "cpu":
+        host = torch.as_tensor(plans)
+        if host.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8):
+            raise C.SrlzError("rollout: plans must be integers (got %s)" % (host.dtype,))
+        if host.numel() and (int(host.min()) < 0 or int(host.max()) >= n_actions):
+            raise C.SrlzError("rollout: plans must hold actions in [0, %d), got %d .. %d" % (n_actions, int(host.min()), int(host.max())))
+        return host.to(torch.int32).contiguous().to(device)
+    if plans.dtype not in (torch.int32, torch.int64):
+        raise C.SrlzError("rollout: device plans must be int32 or int64 (got %s)" % (plans.dtype,))
+    return plans.to(torch.int32).contiguous()
+
+
+def rollout(states, plans, wf, bf, reward=None, final=None, returns=None, trajectory=None, reward_logits=None, gamma=1.0):
+    """One launch of srlz_rollout.  states fp32 [N,S]; plans int [N,K,T] or [K,T] (shared by every environment, read with an
+    environment stride of 0); wf / bf = forward_net.weight [S,S+A] / bias; reward = (w1, b1, w2, b2, w3, b3) of reward_net.0/2/4 or
+    None (no reward work: returns / reward_logits must be None).  `final` [N,K,S] is made here when None; the other outputs are
+    written only when given ([N,K], [N,K,T,S], [N,K,T,2]).  Returns `final`."""
+    states = _rollout_f32(states, "states")
+    if states.dim() != 2:
+        raise C.SrlzError("rollout: states [N,S] expected, got %s" % (tuple(states.shape),))
+    n, s = states.shape
+    wf = _rollout_f32(wf, "forward_net.weight")
+    if wf.dim() != 2 or wf.shape[0] != s or wf.shape[1] <= s:
+        raise C.SrlzError("rollout: forward_net.weight of shape %s does not take states of %d dimensions" % (tuple(wf.shape), s))
+    a = wf.shape[1] - s
+    bf = _rollout_f32(bf, "forward_net.bias", (s,))
+    plans = rollout_plans(plans, a, states.device)
+    if plans.device != states.device or plans.dim() not in (2, 3) or (plans.dim() == 3 and plans.shape[0] != n):
+        raise C.SrlzError("rollout: plans must be [N,K,T] with N = %d or [K,T] on the states' device, got %s" % (n, tuple(plans.shape)))
+    k, t = plans.shape[-2], plans.shape[-1]
+    stride = k * t if plans.dim() == 3 else 0
+    h, head = 0, (None,) * 6
+    if reward is not None:
+        h = reward[0].shape[0]
+        shapes = ((h, 2 * s), (h,), (h, h), (h,), (2, h), (2,))
+        head = tuple(_rollout_f32(p, "reward_net parameter", shape) for p, shape in zip(reward, shapes))
+    if final is None:
+        final = torch.empty((n, k, s), dtype=torch.float32, device=states.device)
+    final = _rollout_f32(final, "final", (n, k, s))
+    returns = _rollout_f32(returns, "returns", (n, k))
+    trajectory = _rollout_f32(trajectory, "trajectory", (n, k, t, s))
+    reward_logits = _rollout_f32(reward_logits, "reward_logits", (n, k, t, 2))
+    C.rollout(ptr(states), ptr(plans), stride, ptr(wf), ptr(bf), *[ptr(p) for p in head], ptr(final), ptr(returns), ptr(trajectory),
+              ptr(reward_logits), n, k, t, s, a, h, 2, float(gamma), stream())
+    return final
