@@ -978,6 +978,42 @@ int srlz_rollout(const float* states, const int* plans, long long plan_env_strid
                  int H, int n_rewards, float gamma, srlz_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Deployment planner (csrc/plan.hip): a categorical cross-entropy method (CEM) over discrete action sequences on the dynamics above,
+ * ONE launch per iteration, enqueued back to back on the caller's stream with no host synchronisation between them; no plan ever
+ * exists on the host.  N environments, K plans each, horizon T, A actions, I = iterations, E = elites, integer sharpness Q, a 64-bit
+ * seed.  Everything is integer arithmetic except the returns:
+ *   table   cum[n][t][a] (uint32) = inclusive prefix sum over a of integer weights w[n][t][a] >= 0.  Iteration 0: w = 1 (init_weights
+ *           NULL), or the caller's init_weights, uint32 [N,T,A] (init_env_stride = T * A) or one [T,A] for every environment (stride
+ *           0); the caller guarantees a positive total below 2^32 in every (n, t) row.
+ *   sample  the action of (iteration i, environment n, plan k, step t): u = word t & 3 of Philox4x32-10 with key (seed & 0xffffffff,
+ *           seed >> 32) and counter (t >> 2, k, n, i); target = (uint64(u) * cum[n][t][A-1]) >> 32; the first a with
+ *           cum[n][t][a] > target.  A sample depends on (seed, i, n, k, t) and its table row alone — not on N, K or the launch.
+ *   score   each plan rolled exactly as srlz_rollout rolls it (the same text, csrc/rollout_tile.h): the return, discounted by gamma,
+ *           has the bits srlz_rollout leaves for the same plan.  The reward head is required.
+ *   select  key = the return, NaN read as -inf; order by key descending, then k ascending; the first E plans are the elites.
+ *   best    iteration 0 stores its top plan and that plan's true return (NaN included); a later iteration replaces them only if its
+ *           top key is strictly greater.
+ *   refit   count[t][a] = elites with action a at step t; w[t][a] = 1 + Q * count[t][a]; cum = its prefix sum.  No momentum.
+ * Outputs: best_plan int32 [N,T], best_return [N], cum uint32 [N,T,A] (the table after the last refit); with plans int32 [I,N,K,T]
+ * and returns [I,N,K] (both or neither) the whole population is kept.
+ * Workspace: srlz_plan_workspace(N, K, T, keep_population) bytes (0 for a refused shape), 16-byte aligned.  Its first N uint32 are the
+ * environments' tickets: zeroed on the stream when the call starts, and zero again when its last launch has ended.
+ * Per launch N * ceil(K / 32) workgroups; the workgroup that finishes an environment last (an integer ticket, no spinning, no grid
+ * barrier) does select, best and refit for it.  Integer LDS atomics for the counts, no float atomics: two runs are bit-identical.
+ * Limits (srlz_plan_supported): those of srlz_rollout_supported and A <= 256, 1 <= K <= 1024, 1 <= T <= 32.  Outside them, a missing
+ * reward head, N < 1, E outside [1, K], I < 1, Q outside [0, 4096], an init stride other than 0 or T * A, half a population:
+ * SRLZ_ERR_BAD_DESC before anything is enqueued, nothing written; a missing required pointer SRLZ_ERR_NULL, a short workspace
+ * SRLZ_ERR_WORKSPACE.
+ * ------------------------------------------------------------------------------------------------------------ */
+int srlz_plan_supported(int S, int A, int H, int n_rewards, int K, int T);
+size_t srlz_plan_workspace(int N, int K, int T, int keep_population);
+int srlz_plan_cem(const float* states, const float* wf, const float* bf, const float* w1, const float* b1, const float* w2,
+                  const float* b2, const float* w3, const float* b3, const unsigned* init_weights, long long init_env_stride,
+                  int* best_plan, float* best_return, unsigned* cum, int* plans, float* returns, void* ws, size_t ws_bytes, int N, int K,
+                  int T, int S, int A, int H, int n_rewards, int iterations, int elites, int sharpness, float gamma,
+                  unsigned long long seed, srlz_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Debug / calibration hooks (not on the product path).
  * ------------------------------------------------------------------------------------------------------------ */
 /* Host-only: dump the virtual-grid program of a 64->64 convolution (tests interpret it on the CPU).

@@ -22,281 +22,42 @@
 // hidden activations 2 * 32 * 33 * 4 = 8.4 KB, W2 / W3 / biases 4.6 KB, row records 0.3 KB: 115 KB of the CU's 160 KB.  A second
 // state tile (S = 1024) does not fit next to that, and H = 64 would be a second MFMA block and twice the partial blocks.
 // 166 VGPRs, no scratch (tools/kres.py): three waves a SIMD by registers, one workgroup a CU by LDS at S = 512, three at S = 200.
+// The tile itself (ro_gemm, the step loop, the reward head) is rollout_tile.h, shared with plan.hip; this file is the rows whose
+// actions come from the caller's plans, and the launcher.
 #include <math.h>
 #include "common.h"
+#include "rollout_tile.h"
+
+using namespace rollout_tile;
 
 namespace {
 
-constexpr int RO_ROWS = 32;     // rows a workgroup owns
-constexpr int RO_LD = 33;       // floats between two k of the state tile / two rows of the small tiles
-constexpr int RO_MAX_S = 512;
-constexpr int RO_MAX_H = 32;
-constexpr int RO_MAX_A = 65536;
-constexpr int RO_WAVES = 8;
-constexpr int RO_THREADS = 64 * RO_WAVES;
-constexpr int RO_KC = 32;       // k of a chunk: the B-operand loads in flight ahead of its 16 MFMAs
-
 struct RolloutArgs {
-  const float* states;   // [N,S]
+  TileArgs tile;
   const int* plans;      // [N,K,T] or [K,T] with env_stride 0
   long long env_stride;  // ints between two environments' plans
-  const float *wf, *bf;  // [S,S+A], [S]
-  const float *w1, *b1, *w2, *b2, *w3, *b3;  // [H,2S],[H],[H,H],[H],[2,H],[2]; w1 == NULL: no reward head
-  float *final_states, *returns, *trajectory, *logits;
-  int R, K, T, S, A, H;
-  float gamma;
+  int R, K;
 };
 
-__host__ __device__ inline int ro_sp(int S) { return (S + RO_KC - 1) & ~(RO_KC - 1); }  // the tile's k, whole chunks
-
-// floats of LDS: state tile, 8 partial blocks, h1, h2, W2, W3, b1, b2, b3 (+2 pad), then 2 * 32 ints
-__host__ __device__ inline size_t ro_lds_bytes(int S, bool reward) {
-  size_t fl = (size_t)ro_sp(S) * RO_LD;
-  if (reward) fl += RO_WAVES * RO_ROWS * RO_LD + 2 * RO_ROWS * RO_LD + RO_MAX_H * RO_MAX_H + 2 * RO_MAX_H + 2 * RO_MAX_H + 4;
-  return (fl + 2 * RO_ROWS) * 4;
-}
-
-// acc += st[32 x k-range] . W[j][koff + k]^T over the chunks c0, c0 + cstep, .. of 32 k each.  w (uniform) + woff (this lane's row
-// and koff, below 2^30 floats at the limits; a row inside the matrix when the lane's column does not exist: jok = false zeroes what
-// it reads).  The k-order inside an MFMA is free as long as both operands agree: lanes 0-31 take k = 32c .. 32c+15 of a chunk, lanes
-// 32-63 k = 32c+16 .. 32c+31, so a lane's share of the B operand is 64 contiguous bytes of its row — four 16-byte loads (rows are only
-// 4-byte aligned: S + A is arbitrary) instead of sixteen dwords from sixteen different cache-line visits.  Whole chunks need no mask;
-// the chunk that holds k = S (if S is no multiple of 32) is read dword by dword, branch-free: a k outside [0, S) reads element 0 of
-// the row and is zeroed.  Its loads are issued first and its MFMAs run last.
-__device__ __forceinline__ void ro_gemm(f32x16& acc, const float* st, const float* __restrict__ w, unsigned woff, bool jok, int S,
-                                        int c0, int cstep, int h, int l31) {
-  constexpr int NK = RO_KC / 2;  // k of a chunk per lane = MFMAs per chunk
-  const int nfull = S / RO_KC;
-  const bool tail = (S % RO_KC) != 0 && nfull >= c0 && (nfull - c0) % cstep == 0;
-  float bt[NK], bn[NK], bc[NK];
-  if (tail) {
-#pragma unroll
-    for (int i = 0; i < NK; ++i) {
-      const int k = RO_KC * nfull + NK * h + i;
-      const bool ok = jok && k < S;
-      const float v = w[woff + (ok ? k : 0)];
-      bt[i] = ok ? v : 0.f;
-    }
+// Rows of a caller's plans: tile row i is row r = row0 + i of the call's R = N * K, environment r / K, plan r % K.
+struct PlanRows {
+  const RolloutArgs& p;
+  const long long row0;
+  const int* myplan = nullptr;  // threads 0..31: row tid's plan
+  __device__ __forceinline__ bool exists(int i) const { return (unsigned)row0 + i < (unsigned)p.R; }  // (R + 32 fits 31 bits: the launcher checks)
+  __device__ __forceinline__ long long env(int i) const { return (long long)(((unsigned)row0 + i) / (unsigned)p.K); }
+  __device__ __forceinline__ long long out(int i) const { return row0 + i; }
+  __device__ __forceinline__ void begin(int i) {
+    const long long r = row0 + i;
+    myplan = p.plans + (r / p.K) * p.env_stride + (r % p.K) * (long long)p.tile.T;
   }
-  auto fetch = [&](int c) {
-    const float* src = w + woff + (RO_KC * c + NK * h);
-#pragma unroll
-    for (int q = 0; q < NK / 4; ++q) {
-      f32x4 v;
-      __builtin_memcpy(&v, src + 4 * q, 16);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) bn[4 * q + e] = v[e];
-    }
-  };
-  auto mfmas = [&](int c, const float (&b)[NK]) {
-    const float* a = st + (RO_KC * c + NK * h) * RO_LD + l31;
-#pragma unroll
-    for (int i = 0; i < NK; ++i) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i * RO_LD], b[i], acc, 0, 0, 0);
-  };
-  if (c0 < nfull) {
-    fetch(c0);
-    for (int c = c0; c < nfull; c += cstep) {
-#pragma unroll
-      for (int i = 0; i < NK; ++i) bc[i] = jok ? bn[i] : 0.f;
-      fetch(c + cstep < nfull ? c + cstep : c);  // (behind the last whole chunk: read it again, dropped)
-      mfmas(c, bc);
-    }
-  }
-  if (tail) mfmas(nfull, bt);
-}
-
-__device__ __forceinline__ float ro_relu(float v) { return v < 0.f ? 0.f : v; }  // NaN stays NaN
+  __device__ __forceinline__ int action(int, int t) const { return myplan[t]; }
+};
 
 __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const RolloutArgs p) {
   extern __shared__ __attribute__((aligned(16))) float ro_lds[];
-  const int S = p.S, A = p.A, H = p.H, T = p.T;
-  const bool reward = p.w1 != nullptr;
-  const int sp = ro_sp(S), nblk = (S + 31) >> 5;
-  float* st = ro_lds;
-  float* fp = st + sp * RO_LD;
-  float *red = nullptr, *h1 = nullptr, *h2 = nullptr, *w2s = nullptr, *w3s = nullptr, *b1s = nullptr, *b2s = nullptr, *b3s = nullptr;
-  if (reward) {
-    red = fp; fp += RO_WAVES * RO_ROWS * RO_LD;
-    h1 = fp; fp += RO_ROWS * RO_LD;
-    h2 = fp; fp += RO_ROWS * RO_LD;
-    w2s = fp; fp += RO_MAX_H * RO_MAX_H;
-    w3s = fp; fp += 2 * RO_MAX_H;
-    b1s = fp; fp += RO_MAX_H;
-    b2s = fp; fp += RO_MAX_H;
-    b3s = fp; fp += 4;
-  }
-  int* act = (int*)fp;        // this step's action of each row, -1 = outside [0, A)
-  int* bad = act + RO_ROWS;   // sticky: the row met an action outside [0, A)
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int h_ = lane >> 5, l31_ = lane & 31;
-  const long long row0 = (long long)blockIdx.x * RO_ROWS;
-  const int ldw = S + A;
-  const float nanf_ = __int_as_float(0x7fc00000);
-
-  // ---- step 0: the rows' states (rows past R and k >= S: zeros), the small reward-head operands, the first actions ----
-  for (int e = tid; e < RO_ROWS * sp; e += RO_THREADS) {
-    const int i = e / sp, k = e - i * sp;
-    const unsigned r = (unsigned)row0 + i;  // (R + 32 fits 31 bits: the launcher checks)
-    float v = 0.f;
-    if (r < (unsigned)p.R && k < S) v = p.states[(long long)(r / (unsigned)p.K) * S + k];
-    st[k * RO_LD + i] = v;
-  }
-  if (reward) {
-    for (int e = tid; e < H * H; e += RO_THREADS) w2s[e] = p.w2[e];
-    for (int e = tid; e < 2 * H; e += RO_THREADS) w3s[e] = p.w3[e];
-    for (int e = tid; e < H; e += RO_THREADS) { b1s[e] = p.b1[e]; b2s[e] = p.b2[e]; }
-    if (tid < 2) b3s[tid] = p.b3[tid];
-  }
-  const int* myplan = nullptr;  // threads 0..31: row tid's plan
-  float ret = 0.f, g = 1.f;
-  if (tid < RO_ROWS) {
-    const long long r = row0 + tid;
-    bad[tid] = 0;
-    if (r < p.R) {
-      myplan = p.plans + (r / p.K) * p.env_stride + (r % p.K) * (long long)T;
-      const int a = myplan[0];
-      const bool ok = (unsigned)a < (unsigned)A;
-      act[tid] = ok ? a : -1;
-      if (!ok) bad[tid] = 1;
-    } else {
-      act[tid] = 0;
-    }
-  }
-  __syncthreads();
-
-  for (int t = 0; t < T; ++t) {
-    // ---- forward model GEMM on s_t, and the s_t half of reward layer 1 ----
-    // (an opaque zero in this step's lane coordinates: without it the compiler computes every GEMM's first addresses and masks once,
-    // outside the step loop, and keeps ~100 registers of them alive through it)
-    int tz = 0;
-    asm volatile("" : "+v"(tz));
-    const int h = h_ + tz, l31 = l31_ + tz;
-    f32x16 acc[2], racc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) racc[r] = 0.f;
-#pragma unroll
-    for (int bi = 0; bi < 2; ++bi) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[bi][r] = 0.f;
-      const int blk = wave + RO_WAVES * bi;
-      if (blk < nblk) {
-        const int j = blk * 32 + l31;
-        const bool jok = j < S;
-        const unsigned woff = (unsigned)(jok ? j : 0) * (unsigned)ldw;
-        // the one-hot's column of each of the lane's 16 rows: requested here, added behind the block's k-loop
-        float wa[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int a = act[(r & 3) + 8 * (r >> 2) + 4 * h];
-          const float v = p.wf[woff + (unsigned)(S + (a >= 0 ? a : 0))];
-          wa[r] = a >= 0 ? v : nanf_;
-        }
-        ro_gemm(acc[bi], st, p.wf, woff, jok, S, 0, 1, h, l31);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[bi][r] = __fadd_rn(acc[bi][r], wa[r]);
-      }
-    }
-    if (reward) ro_gemm(racc, st, p.w1, (unsigned)(l31 < H ? l31 : 0) * (unsigned)(2 * S), l31 < H, S, wave, RO_WAVES, h, l31);
-    __syncthreads();  // every wave has read s_t
-
-    // ---- epilogue: s_{t+1} into the tile ----
-#pragma unroll
-    for (int bi = 0; bi < 2; ++bi) {
-      const int blk = wave + RO_WAVES * bi;
-      const int j = blk * 32 + l31;
-      if (blk < nblk && j < S) {
-        const float bj = p.bf[j];
-        float* sj = st + j * RO_LD;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int i = (r & 3) + 8 * (r >> 2) + 4 * h;
-          const float sn = __fadd_rn(sj[i], __fadd_rn(acc[bi][r], bj));
-          sj[i] = bad[i] ? nanf_ : sn;
-        }
-      }
-    }
-    __syncthreads();  // s_{t+1} is in the tile
-
-    // ---- s_{t+1} out: wave w writes rows 4w .. 4w+3 of the tile, a row's S floats along the lanes ----
-    if (p.trajectory || t == T - 1) {
-      for (int i = wave * (RO_ROWS / RO_WAVES); i < (wave + 1) * (RO_ROWS / RO_WAVES); ++i) {
-        const long long rg = row0 + i;
-        if (rg >= p.R) break;
-        float* tr = p.trajectory ? p.trajectory + (rg * T + t) * S : nullptr;
-        float* fin = t == T - 1 ? p.final_states + rg * S : nullptr;
-        for (int j = lane; j < S; j += 64) {
-          const float v = st[j * RO_LD + i];
-          if (tr) tr[j] = v;
-          if (fin) fin[j] = v;
-        }
-      }
-    }
-
-    if (reward) {
-      // ---- the s_{t+1} half of layer 1, partial blocks to LDS ----
-      ro_gemm(racc, st, p.w1, (unsigned)(l31 < H ? l31 : 0) * (unsigned)(2 * S) + (unsigned)S, l31 < H, S, wave, RO_WAVES, h, l31);
-      if (l31 < H) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int i = (r & 3) + 8 * (r >> 2) + 4 * h;
-          red[(wave * RO_ROWS + i) * RO_LD + l31] = racc[r];
-        }
-      }
-      __syncthreads();
-      const int i = tid & 31, jg = tid >> 5;
-      for (int j = jg; j < H; j += RO_THREADS / 32) {
-        const float* q = red + i * RO_LD + j;
-        float s = q[0];
-#pragma unroll
-        for (int w = 1; w < RO_WAVES; ++w) s = __fadd_rn(s, q[w * RO_ROWS * RO_LD]);
-        h1[i * RO_LD + j] = ro_relu(__fadd_rn(s, b1s[j]));
-      }
-      __syncthreads();
-      for (int j = jg; j < H; j += RO_THREADS / 32) {
-        float s = 0.f;
-        for (int m = 0; m < H; ++m) s = fmaf(h1[i * RO_LD + m], w2s[j * H + m], s);
-        h2[i * RO_LD + j] = ro_relu(__fadd_rn(s, b2s[j]));
-      }
-      __syncthreads();
-    }
-    if (tid < RO_ROWS) {
-      const long long rg = row0 + tid;
-      if (reward) {
-        float l0 = 0.f, l1 = 0.f;
-        for (int m = 0; m < H; ++m) {
-          const float v = h2[tid * RO_LD + m];
-          l0 = fmaf(v, w3s[m], l0);
-          l1 = fmaf(v, w3s[H + m], l1);
-        }
-        l0 = __fadd_rn(l0, b3s[0]);
-        l1 = __fadd_rn(l1, b3s[1]);
-        if (bad[tid]) l0 = l1 = nanf_;
-        const float prob = 1.f / (1.f + expf(l0 - l1));
-        ret = __fadd_rn(ret, __fmul_rn(g, prob));
-        g = __fmul_rn(g, p.gamma);
-        if (rg < p.R) {
-          if (p.logits) {
-            float* o = p.logits + (rg * T + t) * 2;
-            o[0] = l0;
-            o[1] = l1;
-          }
-          if (t == T - 1 && p.returns) p.returns[rg] = ret;
-        }
-      }
-      if (t + 1 < T && myplan) {  // the next step's action (read by the epilogue, two barriers from here)
-        const int a = myplan[t + 1];
-        const bool ok = (unsigned)a < (unsigned)A;
-        act[tid] = ok ? a : -1;
-        if (!ok) bad[tid] = 1;
-      }
-    }
-    __syncthreads();
-  }
-}
-
-int ro_supported(int S, int A, int H, int n_rewards) {
-  return S >= 1 && S <= RO_MAX_S && A >= 1 && A <= RO_MAX_A && H >= 1 && H <= RO_MAX_H && n_rewards == 2;
+  PlanRows rows{p, (long long)blockIdx.x * RO_ROWS};
+  ro_tile(p.tile, ro_lds, rows);
 }
 
 }  // namespace
@@ -325,8 +86,8 @@ extern "C" int srlz_rollout(const float* states, const int* plans, long long pla
                "rollout: returns / reward_logits asked for without a reward head");
   SRLZ_REQUIRE(states && plans && wf && bf && final_states, SRLZ_ERR_NULL, "rollout: null pointer");
   const int R = N * K;
-  RolloutArgs a{states, plans, plan_env_stride, wf, bf, w1, b1, w2, b2, w3, b3, final_states, returns, trajectory, reward_logits,
-                R, K, T, S, A, reward ? H : 0, gamma};
+  RolloutArgs a{{states, wf, bf, w1, b1, w2, b2, w3, b3, final_states, returns, trajectory, reward_logits, T, S, A, reward ? H : 0, gamma},
+                plans, plan_env_stride, R, K};
   const size_t lds = ro_lds_bytes(S, reward);
   SRLZ_MAX_LDS(rollout_kernel, lds);
   SRLZ_LAUNCH(rollout_kernel, dim3((unsigned)((R + RO_ROWS - 1) / RO_ROWS)), dim3(RO_THREADS), lds, as_stream(stream), a);

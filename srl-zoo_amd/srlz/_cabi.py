@@ -6,7 +6,7 @@ There is NO fallback: if the library is missing the import fails loudly, and eve
 """
 import ctypes
 import os
-from ctypes import c_int, c_longlong, c_float, c_double, c_void_p, c_size_t, c_char_p, POINTER, Structure
+from ctypes import c_int, c_longlong, c_ulonglong, c_float, c_double, c_void_p, c_size_t, c_char_p, POINTER, Structure
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsrlz_hip.so")
@@ -275,6 +275,10 @@ _PROTOS = {
     "srlz_rollout_tile": (c_int, []),
     "srlz_rollout": (c_int, [P, P, c_longlong, P, P, P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                              c_float, P]),
+    "srlz_plan_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "srlz_plan_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "srlz_plan_cem": (c_int, [P, P, P, P, P, P, P, P, P, P, c_longlong, P, P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int,
+                              c_int, c_int, c_int, c_int, c_int, c_float, c_ulonglong, P]),
 }
 
 # entry points whose int return value is data, not a status
@@ -288,7 +292,7 @@ _NOT_STATUS = {"srlz_version", "srlz_device_cus", "srlz_conv64_fwd_tiles", "srlz
                "srlz_dense_out_fwd_loss_workgroups", "srlz_reward_probe_chunk_rows", "srlz_infer_block_supported",
                "srlz_infer_tile", "srlz_conv64_bwd_fused_workgroups", "srlz_conv1_workgroups",
                "srlz_conv1_buffer_staging_supported", "srlz_infer_dec_supported", "srlz_infer_dec_tile", "srlz_rollout_supported",
-               "srlz_rollout_tile"}
+               "srlz_rollout_tile", "srlz_plan_supported"}
 
 EXPORTED = sorted(_PROTOS.keys())
 

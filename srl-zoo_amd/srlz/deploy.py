@@ -24,8 +24,8 @@ model's mode or torch's RNG, and runs on the current stream.  The states it retu
 overwritten by the next call (clone them to keep them), and one encoder serves one stream at a time.
 
 The way back — FrameDecoder, states to camera frames in six launches, and reconstruct(encoder, decoder, frames) — is the second half
-of this file; LatentDynamics — states and plans through the forward and reward heads to returns in one launch — and imagine are the
-third part.
+of this file; LatentDynamics — states and plans through the forward and reward heads to returns in one launch — imagine, and the
+planner LatentDynamics.plan — a cross-entropy search on the device, one launch per iteration — are the third part.
 """
 import numpy as np
 import torch
@@ -574,6 +574,26 @@ def reconstruct(encoder, decoder, frames):
 # A "rollout" call launches on the current stream into buffers made at construction (states, plans, final states, returns, and the
 # trajectory / logits buffers of max_rows * max_horizon steps), builds no graph, and leaves modes, parameters and torch's RNG alone.
 # What it returns are views of those buffers, valid until the next call.
+#
+# The planner.  act scores plans the caller brings; a controller has a state and wants an action:
+#     p = dyn.plan(states, horizon, n_plans=64, iterations=4, elites=8, sharpness=8, gamma=1.0, seed=0, init_weights=None,
+#                  keep_population=False)
+#     p.best_plan, p.best_return, p.action, p.weights     # int32 [N,T], fp32 [N], int64 [N] (= best_plan[:, 0]), int32 [N,T,A]
+#     p.plans, p.returns                                  # keep_population: int32 [I,N,K,T], fp32 [I,N,K]; else None
+#     p.shifted()                                         # the table one step ahead: the next call's init_weights
+# A categorical cross-entropy method over discrete action sequences, stated exactly in include/srlz.h: a table of integer weights
+# per (environment, step, action), uniform or the caller's init_weights ([T,A] or [N,T,A]); each of `iterations` rounds samples
+# n_plans plans per environment from it (Philox4x32-10, counter (t >> 2, k, n, i), key = the 64-bit seed), rolls them as rollout
+# does, ranks them (return descending — NaN as -inf — then k ascending), keeps the best plan seen so far (replaced only by a strictly
+# greater key) and refits the table to w = 1 + sharpness * (elites with that action at that step).  Everything but the returns is
+# integer arithmetic: a call is a function of its inputs and the seed, bit for bit.  Route "rollout" is `iterations` launches of
+# csrc/plan.hip back to back on the current stream, no host synchronisation between them and no plan on the host; the returns are the
+# bits dyn.rollout gives for the same plans.  Route "model" runs the same algorithm in numpy (cem_host) over this object's own
+# returns (_run): SRLModulesSplit, shapes srlz_plan_supported refuses (more than 256 actions, 1024 plans or 32 steps) and calls of
+# more than max_rows rows — nothing is rejected for size.  The reward head is required (the gating ValueError of act).  The planner's
+# buffers are made on the first plan call and grown only when a call asks for more; what a call returns are views of them, valid
+# until the next call (shifted() is a new tensor).  Device init_weights — a Plan's shifted() — are taken as they are; host ones are
+# checked: non-negative, every row with a positive total.
 # =============================================================================================================
 ROUTE_ROLLOUT = "rollout"
 HEADS = ("forward", "inverse", "reward")
@@ -655,6 +675,153 @@ def check_plans(plans, n, n_actions):
     return (shape[-2] if len(shape) > 1 else 1), shape[-1], len(shape) < 3, len(shape) == 1
 
 
+# ---- the planner's host side: argument checks, the route table and the same algorithm in numpy (route "model") ----
+PLAN_MAX_SHARPNESS = 4096
+
+
+class Plan(object):
+    """What LatentDynamics.plan returns.  best_plan int32 [N,T], best_return fp32 [N], action int64 [N] (= best_plan[:, 0], as act
+    returns it), weights int32 [N,T,A] (the final table's integer weights), plans int32 [I,N,K,T] and returns fp32 [I,N,K] (the
+    whole population) or None; a bare state drops the N axis everywhere.  All on the device."""
+    __slots__ = ("best_plan", "best_return", "action", "weights", "plans", "returns")
+
+    def __init__(self, best_plan, best_return, action, weights, plans=None, returns=None):
+        self.best_plan, self.best_return, self.action, self.weights, self.plans, self.returns = \
+            best_plan, best_return, action, weights, plans, returns
+
+    def shifted(self):
+        """The table moved one step ahead — step 0 dropped, a uniform last step: the init_weights of the controller's next call."""
+        w = self.weights
+        return torch.cat((w[..., 1:, :], torch.ones_like(w[..., :1, :])), dim=-2)
+
+
+def check_plan_args(horizon, n_plans, iterations, elites, sharpness, seed):
+    """Validate a plan call's numbers (host only).  Returns them as ints: (horizon, n_plans, iterations, elites, sharpness, seed)."""
+    vals = []
+    for name, v in (("horizon", horizon), ("n_plans", n_plans), ("iterations", iterations), ("elites", elites), ("sharpness", sharpness),
+                    ("seed", seed)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+        vals.append(int(v))
+    t, k, it, e, q, seed = vals
+    if t < 1 or k < 1 or it < 1:
+        raise ValueError("horizon, n_plans and iterations must be at least 1, got %d, %d and %d" % (t, k, it))
+    if not 1 <= e <= k:
+        raise ValueError("elites must lie in [1, n_plans = %d], got %d" % (k, e))
+    if not 0 <= q <= PLAN_MAX_SHARPNESS:
+        raise ValueError("sharpness must lie in [0, %d], got %d" % (PLAN_MAX_SHARPNESS, q))
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("seed must be a 64-bit unsigned integer, got %d" % seed)
+    return t, k, it, e, q, seed
+
+
+def check_init_weights(init_weights, n, horizon, n_actions):
+    """Validate a plan call's init_weights: None, or integers [T,A] / [N,T,A]; host weights non-negative, below 2^31, every (n, t) row
+    with a positive total below 2^32 (device weights — a Plan's shifted() — are taken as they are).  Returns (weights, shared)."""
+    if init_weights is None:
+        return None, True
+    if not isinstance(init_weights, (np.ndarray, torch.Tensor)):
+        raise ValueError("init_weights must be a numpy array or a torch tensor, got %s" % type(init_weights).__name__)
+    is_int = np.issubdtype(init_weights.dtype, np.integer) if isinstance(init_weights, np.ndarray) else \
+        init_weights.dtype in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)
+    if not is_int:
+        raise ValueError("init_weights must be integers (got %s)" % (init_weights.dtype,))
+    shape = tuple(init_weights.shape)
+    if shape not in ((horizon, n_actions), (n, horizon, n_actions)):
+        raise ValueError("init_weights must be [T,A] = %s or [N,T,A] = %s, got shape %s"
+                         % ((horizon, n_actions), (n, horizon, n_actions), shape))
+    if isinstance(init_weights, np.ndarray) or init_weights.device.type == "cpu":
+        host = np.asarray(init_weights).astype(np.int64)
+        if host.min() < 0 or host.max() >= 2 ** 31:
+            raise ValueError("init_weights must be non-negative and below 2^31, got %d .. %d" % (host.min(), host.max()))
+        totals = host.sum(axis=-1)
+        if totals.min() < 1 or totals.max() >= 2 ** 32:
+            raise ValueError("every row of init_weights needs a positive total below 2^32, got totals %d .. %d" % (totals.min(), totals.max()))
+        init_weights = host
+    return init_weights, len(shape) == 2
+
+
+def plan_route_for(model, n_plans, horizon, n_envs=1, max_rows=8192):
+    """The route LatentDynamics.plan takes for a call of n_envs states (host only: no GPU is asked for)."""
+    if dynamics_route_for(model) != ROUTE_ROLLOUT or n_envs * n_plans > max_rows:
+        return ROUTE_MODEL
+    s, a, h, nr = dynamics_dims(model)
+    return ROUTE_ROLLOUT if ops.plan_supported(s, a, h, nr, n_plans, horizon) else ROUTE_MODEL
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 on numpy uint64 arrays of 32-bit words: counter (c0, c1, c2, c3), key (k0, k1) -> four words."""
+    lo32 = np.uint64(0xFFFFFFFF)
+    c0, c1, c2, c3 = [np.asarray(c, np.uint64) for c in counter]
+    k0, k1 = np.uint64(key[0]), np.uint64(key[1])
+    for _ in range(10):
+        a, b = c0 * np.uint64(0xD2511F53), c2 * np.uint64(0xCD9E8D57)
+        c0, c1, c2, c3 = (b >> np.uint64(32)) ^ c1 ^ k0, b & lo32, (a >> np.uint64(32)) ^ c3 ^ k1, a & lo32
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & lo32, (k1 + np.uint64(0xBB67AE85)) & lo32
+    return c0, c1, c2, c3
+
+
+def sample_actions(u, cum_row):
+    """Actions of the 32-bit draws u on one table row (uint32 prefix sums): the first a with cum[a] > (u * cum[A-1]) >> 32."""
+    row = np.asarray(cum_row, np.uint64)
+    target = (np.asarray(u, np.uint64) * row[-1]) >> np.uint64(32)
+    return np.searchsorted(row, target, side="right").astype(np.int32)
+
+
+def sample_plans(cum, seed, iteration, n_plans):
+    """int32 [N,K,T]: the population of one iteration from the table cum [N,T,A]."""
+    n, t, _ = cum.shape
+    key = (seed & 0xFFFFFFFF, seed >> 32)
+    plans = np.empty((n, n_plans, t), np.int32)
+    ks = np.arange(n_plans, dtype=np.uint64)
+    for e in range(n):
+        for t4 in range(0, t, 4):
+            words = philox4x32_10((np.full_like(ks, t4 >> 2), ks, np.full_like(ks, e), np.full_like(ks, iteration)), key)
+            for step in range(t4, min(t4 + 4, t)):
+                plans[e, :, step] = sample_actions(words[step & 3], cum[e, step])
+    return plans
+
+
+def weights_of_table(cum):
+    return np.diff(np.asarray(cum).astype(np.int64), axis=-1, prepend=0)
+
+
+def cem_host(returns_fn, n, n_plans, horizon, n_actions, iterations, elites, sharpness, seed, init_weights=None, keep_population=False):
+    """The planner on the host, the algorithm of csrc/plan.hip in numpy over returns_fn(plans int32 [N,K,T]) -> fp32 [N,K].
+    Returns a dict: best_plan [N,T], best_return [N], cum uint32 [N,T,A], history [I,N] (the best key after each iteration), and with
+    keep_population plans [I,N,K,T] and returns [I,N,K]."""
+    if init_weights is None:
+        w = np.ones((n, horizon, n_actions), np.uint64)
+    else:
+        w = np.broadcast_to(np.asarray(init_weights).astype(np.uint64), (n, horizon, n_actions))
+    cum = np.cumsum(w, axis=2).astype(np.uint32)
+    best_plan, best_return = np.zeros((n, horizon), np.int32), np.zeros(n, np.float32)
+    best_key = np.full(n, -np.inf, np.float32)
+    pops, rets, history = [], [], []
+    steps = np.arange(horizon)
+    for i in range(iterations):
+        plans = sample_plans(cum, seed, i, n_plans)
+        returns = np.asarray(returns_fn(plans), np.float32).reshape(n, n_plans)
+        keys = np.where(np.isnan(returns), np.float32(-np.inf), returns)
+        for e in range(n):
+            order = np.argsort(-keys[e], kind="stable")[:elites]  # key descending, ties in k ascending
+            top = order[0]
+            if i == 0 or keys[e, top] > best_key[e]:
+                best_key[e], best_return[e], best_plan[e] = keys[e, top], returns[e, top], plans[e, top]
+            count = np.zeros((horizon, n_actions), np.uint64)
+            for el in order:
+                np.add.at(count, (steps, plans[e, el]), np.uint64(1))
+            cum[e] = np.cumsum(np.uint64(1) + np.uint64(sharpness) * count, axis=1).astype(np.uint32)
+        history.append(best_key.copy())
+        if keep_population:
+            pops.append(plans)
+            rets.append(returns)
+    out = dict(best_plan=best_plan, best_return=best_return, cum=cum, history=np.stack(history))
+    if keep_population:
+        out["plans"], out["returns"] = np.stack(pops), np.stack(rets)
+    return out
+
+
 class LatentDynamics(object):
     def __init__(self, model, max_rows=8192, max_horizon=32, untrained_ok=False, route=None):
         """model: SRLModules / SRLModulesSplit / a learner.  max_rows: N * K rows a "rollout" call may take, max_horizon: its steps;
@@ -673,6 +840,7 @@ class LatentDynamics(object):
         _requireGpu(True)
         self.max_rows, self.max_horizon = int(max_rows), int(max_horizon)
         self._route, self.last_route = picked, None
+        self._plan_bufs = {}  # the planner's device buffers: made by the first plan call
         self.device = next(self.owner.forward_net.parameters()).device
         if self.device.type != "cuda":
             raise C.SrlzError("LatentDynamics: the model must live on the GPU (there is no CPU path)")
@@ -849,6 +1017,75 @@ class LatentDynamics(object):
         first = pl[..., 0].to(torch.int64)  # [n,k] or (shared) [k]
         a = first[best] if first.dim() == 1 else first.gather(1, best.unsqueeze(1)).squeeze(1)
         return a[0] if single else a
+
+    def _plan_buffers(self, n, k, t, iterations, keep):
+        """The planner's device buffers, made on the first plan call and grown only when a call asks for more."""
+        a = self.n_actions
+        want = dict(best=n * t, ret=n, cum=n * t * a, ws=ops.plan_workspace(n, k, t, keep), pop=iterations * n * k * t if keep else 0,
+                    pret=iterations * n * k if keep else 0, init=n * t * a, w=n * t * a, act=n)
+        kinds = dict(best=torch.int32, ret=torch.float32, cum=torch.int32, ws=torch.uint8, pop=torch.int32, pret=torch.float32,
+                     init=torch.int32, w=torch.int32, act=torch.int64)
+        have = self._plan_bufs
+        for name, numel in want.items():
+            if name not in have or have[name].numel() < numel:
+                have[name] = torch.empty(max(numel, 1), dtype=kinds[name], device=self.device)
+        return have
+
+    def plan(self, states, horizon, n_plans=64, iterations=4, elites=8, sharpness=8, gamma=1.0, seed=0, init_weights=None,
+             keep_population=False):
+        """A categorical cross-entropy search for each environment's action sequence (the comment block above states it) -> Plan."""
+        self._need("forward")
+        self._need("reward")
+        n, single = check_states(states, self.state_dim)
+        t, k, it, e, q, seed = check_plan_args(horizon, n_plans, iterations, elites, sharpness, seed)
+        init_weights, shared = check_init_weights(init_weights, n, t, self.n_actions)
+        a = self.n_actions
+        kernel = self._route == ROUTE_ROLLOUT and n * k <= self.max_rows and \
+            ops.plan_supported(self.state_dim, a, self._h, self._nr, k, t)
+        if not kernel:
+            host_w = init_weights.cpu().numpy() if torch.is_tensor(init_weights) else init_weights
+
+            def returns_fn(pl):
+                return self._run(states, pl[0] if single else pl, float(gamma), True, False, False)[1].reshape(n, k).cpu().numpy()
+            out = cem_host(returns_fn, n, k, t, a, it, e, q, seed, host_w, keep_population)
+            self.last_route = ROUTE_MODEL
+            dev = self.device
+            best_plan = torch.from_numpy(out["best_plan"]).to(dev)
+            best_return = torch.from_numpy(out["best_return"]).to(dev)
+            weights = torch.from_numpy(weights_of_table(out["cum"]).astype(np.int32)).to(dev)
+            plans = torch.from_numpy(out["plans"]).to(dev) if keep_population else None
+            returns = torch.from_numpy(out["returns"]).to(dev) if keep_population else None
+        else:
+            self.last_route = ROUTE_ROLLOUT
+            x = self._device_states(states, n, single, True)
+            b = self._plan_buffers(n, k, t, it, keep_population)
+            iw = None
+            if init_weights is not None:
+                shape = (t, a) if shared else (n, t, a)
+                iw = b["init"][:int(np.prod(shape))].view(shape)
+                iw.copy_(torch.from_numpy(init_weights.astype(np.int32)) if isinstance(init_weights, np.ndarray) else init_weights,
+                         non_blocking=True)
+            best_plan, best_return = b["best"][:n * t].view(n, t), b["ret"][:n]
+            cum = b["cum"][:n * t * a].view(n, t, a)
+            plans = b["pop"][:it * n * k * t].view(it, n, k, t) if keep_population else None
+            returns = b["pret"][:it * n * k].view(it, n, k) if keep_population else None
+            o, rn = self.owner, self.owner.reward_net
+            head = (rn[0].weight, rn[0].bias, rn[2].weight, rn[2].bias, rn[4].weight, rn[4].bias)
+            ops.plan_cem(x, o.forward_net.weight, o.forward_net.bias, head, k, t, it, e, q, best_plan, best_return, cum, b["ws"],
+                         gamma=gamma, seed=seed, init_weights=iw, plans=plans, returns=returns)
+            weights = b["w"][:n * t * a].view(n, t, a)  # (the table's uint32 stay below 2^31 at these limits)
+            weights[:, :, :1].copy_(cum[:, :, :1])
+            if a > 1:
+                torch.sub(cum[:, :, 1:], cum[:, :, :-1], out=weights[:, :, 1:])
+            action = b["act"][:n]
+            action.copy_(best_plan[:, 0])
+        if not kernel:
+            action = best_plan[:, 0].to(torch.int64)
+        if single:
+            best_plan, best_return, action, weights = best_plan[0], best_return[0], action[0], weights[0]
+            plans = plans[:, 0] if plans is not None else None
+            returns = returns[:, 0] if returns is not None else None
+        return Plan(best_plan, best_return, action, weights, plans, returns)
 
     def _pair(self, states, next_states):
         n, single = check_states(states, self.state_dim)

@@ -2285,3 +2285,64 @@ def rollout(states, plans, wf, bf, reward=None, final=None, returns=None, trajec
     C.rollout(ptr(states), ptr(plans), stride, ptr(wf), ptr(bf), *[ptr(p) for p in head], ptr(final), ptr(returns), ptr(trajectory),
               ptr(reward_logits), n, k, t, s, a, h, 2, float(gamma), stream())
     return final
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# Deployment planner (csrc/plan.hip): a categorical cross-entropy method on the dynamics above, one launch per iteration, all of them
+# enqueued here back to back.  Thin, as rollout: the caller owns every buffer, nothing is allocated and no autograd node is made.
+# ----------------------------------------------------------------------------------------------------------------
+def plan_supported(s, a, h, n_rewards, n_plans, horizon):
+    return bool(C.plan_supported(int(s), int(a), int(h), int(n_rewards), int(n_plans), int(horizon)))
+
+
+def plan_workspace(n, n_plans, horizon, keep_population=False):
+    """Bytes of workspace of a plan_cem call; 0 for a shape it refuses."""
+    return int(C.plan_workspace(int(n), int(n_plans), int(horizon), int(bool(keep_population))))
+
+
+def _plan_buf(t, name, dtype, shape):
+    if t is None:
+        return None
+    if not torch.is_tensor(t) or t.device.type != "cuda" or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise C.SrlzError("plan_cem: %s must be a contiguous %s device tensor of shape %s" % (name, dtype, tuple(shape)))
+    return t
+
+
+def plan_cem(states, wf, bf, reward, n_plans, horizon, iterations, elites, sharpness, best_plan, best_return, cum, workspace,
+             gamma=1.0, seed=0, init_weights=None, plans=None, returns=None):
+    """`iterations` launches of plan_cem_kernel.  states fp32 [N,S]; wf / bf / reward = (w1 .. b3) as rollout takes them (the reward
+    head is required); init_weights None (uniform) or int32 [N,T,A] / [T,A] on the device, every row's total positive and below 2^32;
+    outputs best_plan int32 [N,T], best_return fp32 [N], cum int32 [N,T,A] (the bits are uint32); plans int32 [I,N,K,T] and returns
+    fp32 [I,N,K] keep the whole population (both or neither); workspace: a uint8 device tensor of plan_workspace(...) bytes."""
+    states = _rollout_f32(states, "states")
+    if states.dim() != 2:
+        raise C.SrlzError("plan_cem: states [N,S] expected, got %s" % (tuple(states.shape),))
+    n, s = states.shape
+    wf = _rollout_f32(wf, "forward_net.weight")
+    if wf.dim() != 2 or wf.shape[0] != s or wf.shape[1] <= s:
+        raise C.SrlzError("plan_cem: forward_net.weight of shape %s does not take states of %d dimensions" % (tuple(wf.shape), s))
+    a = wf.shape[1] - s
+    bf = _rollout_f32(bf, "forward_net.bias", (s,))
+    if reward is None:
+        raise C.SrlzError("plan_cem: the planner scores by the reward head")
+    h = reward[0].shape[0]
+    shapes = ((h, 2 * s), (h,), (h, h), (h,), (2, h), (2,))
+    head = tuple(_rollout_f32(p, "reward_net parameter", shape) for p, shape in zip(reward, shapes))
+    k, t, it = int(n_plans), int(horizon), int(iterations)
+    stride = 0
+    if init_weights is not None:
+        if tuple(init_weights.shape) not in ((t, a), (n, t, a)):
+            raise C.SrlzError("plan_cem: init_weights must be [T,A] or [N,T,A], got %s" % (tuple(init_weights.shape),))
+        stride = t * a if init_weights.dim() == 3 else 0
+        init_weights = _plan_buf(init_weights, "init_weights", torch.int32, init_weights.shape)
+    best_plan = _plan_buf(best_plan, "best_plan", torch.int32, (n, t))
+    best_return = _plan_buf(best_return, "best_return", torch.float32, (n,))
+    cum = _plan_buf(cum, "cum", torch.int32, (n, t, a))
+    plans = _plan_buf(plans, "plans", torch.int32, (it, n, k, t))
+    returns = _plan_buf(returns, "returns", torch.float32, (it, n, k))
+    if not torch.is_tensor(workspace) or workspace.device.type != "cuda" or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise C.SrlzError("plan_cem: workspace must be a contiguous uint8 device tensor")
+    C.plan_cem(ptr(states), ptr(wf), ptr(bf), *[ptr(p) for p in head], ptr(init_weights), stride, ptr(best_plan), ptr(best_return),
+               ptr(cum), ptr(plans), ptr(returns), ptr(workspace), workspace.numel(), n, k, t, s, a, h, 2, it, int(elites),
+               int(sharpness), float(gamma), int(seed) & 0xFFFFFFFFFFFFFFFF, stream())
+    return best_plan
