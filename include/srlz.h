@@ -1014,6 +1014,47 @@ int srlz_plan_cem(const float* states, const float* wf, const float* bf, const f
                   unsigned long long seed, srlz_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Goal-distance scores (csrc/rollout_tile.h, instantiated in rollout.hip and plan.hip): "drive the learned state to the state of this
+ * goal picture".  The rollout and the planner above with one more term per step, composed on the same reference lines —
+ * forwardModel (models/forward_inverse.py:21-31) for the states, rewardModel (:78-95) for prob_t when a reward head is given.
+ * Per row, a goal goal[n] (fp32 [S]), a weight w > 0 and a mode; at step t, once s_{t+1} is in the tile:
+ *   d_t    = sum_j fl(s_{t+1}[j] - goal[j])^2                            fp32, the order below
+ *   c_t    = d_t (goal_mode 0, running)  |  d_t if t == T-1 else 0 (goal_mode 1, final)
+ *   term_t = reward head given ?  fl(prob_t - fl(w * c_t))  :  -fl(w * c_t)     prob_t = 1 / (1 + exp(l0 - l1)) as above
+ *   ret    = fl(ret + fl(g_t * term_t));   g_0 = 1, g_{t+1} = fl(g_t * gamma)     (g advances with or without a reward head)
+ * returns [N,K] holds ret: the score, and the planner's key under the rule above (NaN read as -inf).  goal_dist [N,K,T] (optional)
+ * holds d_t of every step in both modes.
+ * Order of d_t, a function of S alone: 16 partial sums, partial q over j = q, q + 16, q + 32, .. ascending, each
+ * p = fma(e, e, p) from p = 0 with e = fl(s_{t+1}[j] - goal[j]); then d_t = ((p_0 + p_1) + p_2) + .. + p_15, each add rounded.  (A partial
+ * whose q >= S is 0.)  No atomics: two runs are bit-identical, a row's outputs do not depend on the other rows, and trajectory,
+ * final_states and reward_logits are the bits srlz_rollout leaves.  A row that met an action outside [0, A) has NaN d_t from that
+ * step on (its states are NaN), and a NaN ret.
+ * goal: fp32 [N,S] (goal_env_stride = S) or one [S] shared by every environment (goal_env_stride = 0, nothing is copied).
+ * The six reward pointers are all given or all NULL; NULL: the score is the goal term alone, returns is still allowed,
+ * reward_logits must be NULL.  The planner's sampling, tickets, select, best and refit are those of srlz_plan_cem; only the key's
+ * source differs.  srlz_plan_goal_workspace equals srlz_plan_workspace.
+ * Limits (srlz_rollout_goal_supported / srlz_plan_goal_supported; has_reward = 0: H and n_rewards are not looked at): those of
+ * srlz_rollout_supported / srlz_plan_supported — the 16 x 33 partials add 2.1 KB of LDS: 117 KB (rollout) and 157.8 KB (planner at
+ * S = 512, H = 32, T = 32, A = 256, K = 1024) of 160.  Outside them, a partly given head, goal_weight not finite or not > 0,
+ * goal_mode other than 0 or 1, a goal stride other than 0 or S, and whatever the call without a goal refuses: SRLZ_ERR_BAD_DESC
+ * before any launch, nothing written; a missing required pointer (goal among them) SRLZ_ERR_NULL.
+ * ------------------------------------------------------------------------------------------------------------ */
+int srlz_rollout_goal_supported(int S, int A, int H, int n_rewards, int has_reward);
+int srlz_rollout_goal(const float* states, const int* plans, long long plan_env_stride, const float* wf, const float* bf,
+                      const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
+                      float* final_states, float* returns, float* trajectory, float* reward_logits, int N, int K, int T, int S, int A,
+                      int H, int n_rewards, float gamma, const float* goal, long long goal_env_stride, float goal_weight,
+                      int goal_mode, float* goal_dist, srlz_stream_t stream);
+int srlz_plan_goal_supported(int S, int A, int H, int n_rewards, int has_reward, int K, int T);
+size_t srlz_plan_goal_workspace(int N, int K, int T, int keep_population);
+int srlz_plan_cem_goal(const float* states, const float* wf, const float* bf, const float* w1, const float* b1, const float* w2,
+                       const float* b2, const float* w3, const float* b3, const unsigned* init_weights, long long init_env_stride,
+                       int* best_plan, float* best_return, unsigned* cum, int* plans, float* returns, void* ws, size_t ws_bytes, int N,
+                       int K, int T, int S, int A, int H, int n_rewards, int iterations, int elites, int sharpness, float gamma,
+                       unsigned long long seed, const float* goal, long long goal_env_stride, float goal_weight, int goal_mode,
+                       srlz_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Debug / calibration hooks (not on the product path).
  * ------------------------------------------------------------------------------------------------------------ */
 /* Host-only: dump the virtual-grid program of a 64->64 convolution (tests interpret it on the CPU).

@@ -17,7 +17,10 @@
 // elites land in their slots without atomics; the action counts are integers, added with LDS integer atomics — one value whatever
 // the order.  No float atomics.  The finisher reads other workgroups' returns and plans past its own L1 (agent-scope loads).
 // LDS at the limits (S = 512, H = 32, T = 32, A = 256, K = 1024): tile 114.7 KB + table 32 KB + keys and elites 8 KB = 155.7 KB of 160.
+// With a goal (plan_cem_kernel<PlanGoalArgs>, srlz_plan_cem_goal): the tile's goal term compiled in, + 2.1 KB for its partials =
+// 157.8 KB; the key is then the score of include/srlz.h, the reward head optional.  Everything else is the same text.
 #include <math.h>
+#include <type_traits>
 #include "common.h"
 #include "rollout_tile.h"
 
@@ -91,13 +94,22 @@ struct SampledRows {
 template <class T>
 __device__ __forceinline__ T load_agent(const T* q) { return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-__global__ __launch_bounds__(RO_THREADS) void plan_cem_kernel(const PlanArgs p) {
+// The planner's arguments with a goal: the key is then the score with the goal term, and the reward head optional.
+struct PlanGoalArgs : PlanArgs {
+  GoalArgs goal;
+};
+
+// One iteration for one tile of one environment: plan_cem_kernel<PlanArgs> (srlz_plan_cem) and plan_cem_kernel<PlanGoalArgs>
+// (srlz_plan_cem_goal) — sampling, tickets, select, best and refit are this one text either way; only the key's source differs.
+template <class Args>
+__global__ __launch_bounds__(RO_THREADS) void plan_cem_kernel(const Args p) {
+  constexpr bool Goal = std::is_same<Args, PlanGoalArgs>::value;
   extern __shared__ __attribute__((aligned(16))) float pl_lds[];
   __shared__ int last;
   const int T = p.tile.T, A = p.tile.A, K = p.K, TA = T * A;
   const int tid = threadIdx.x;
   const int n = blockIdx.x / p.tiles, tile = blockIdx.x - n * p.tiles;
-  unsigned* tab = (unsigned*)((char*)pl_lds + ro_lds_bytes(p.tile.S, true));  // [T,A]; the finisher's counts afterwards
+  unsigned* tab = (unsigned*)((char*)pl_lds + ro_lds_bytes(p.tile.S, !Goal || p.tile.w1 != nullptr, Goal));  // [T,A]; the finisher's counts afterwards
   float* keys = (float*)(tab + TA);                                             // [K]
   int* elite = (int*)(keys + K);                                                // [E]
 
@@ -118,7 +130,8 @@ __global__ __launch_bounds__(RO_THREADS) void plan_cem_kernel(const PlanArgs p) 
   __syncthreads();
 
   SampledRows rows{p, tab, n, tile * RO_ROWS};
-  ro_tile(p.tile, pl_lds, rows);
+  if constexpr (Goal) ro_tile<SampledRows, true>(p.tile, pl_lds, rows, &p.goal);
+  else ro_tile(p.tile, pl_lds, rows);
 
   // ---- the environment's last workgroup to finish goes on ----
   // (ro_tile ended behind a workgroup barrier: every wave's stores happen before thread 0's fence, which releases them all)
@@ -176,6 +189,11 @@ __global__ __launch_bounds__(RO_THREADS) void plan_cem_kernel(const PlanArgs p) 
   }
 }
 
+// LDS of a launch: the tile, the table [T,A], keys [K] and elites (at most K)
+size_t pl_lds_bytes(int S, bool reward, bool goal, int K, int T, int A) {
+  return ro_lds_bytes(S, reward, goal) + ((size_t)T * A + 2 * (size_t)K) * 4;
+}
+
 int pl_supported(int S, int A, int H, int n_rewards, int K, int T) {
   return ro_supported(S, A, H, n_rewards) && A <= PL_MAX_A && K >= 1 && K <= PL_MAX_K && T >= 1 && T <= PL_MAX_T;
 }
@@ -185,6 +203,12 @@ size_t pl_workspace(long long N, int K, int T, bool keep) {
   size_t b = (size_t)N * 8;
   if (!keep) b += (size_t)N * K * 4 + (size_t)N * K * T * 4;
   return b;
+}
+
+// With the goal term: the tile's own answer, the planner's limits, and the whole launch (+ the ticket flag) inside the CU's LDS.
+int pl_goal_supported(int S, int A, int H, int n_rewards, int has_reward, int K, int T) {
+  return ro_goal_supported(S, A, H, n_rewards, has_reward) && A <= PL_MAX_A && K >= 1 && K <= PL_MAX_K && T >= 1 && T <= PL_MAX_T &&
+         pl_lds_bytes(S, has_reward != 0, true, K, T, A) + 16 <= RO_LDS_CAP;
 }
 
 bool pl_rows_ok(int N, int K) { return N >= 1 && K >= 1 && K <= PL_MAX_K && (long long)N * K <= 0x7fffffffLL - RO_ROWS; }
@@ -230,13 +254,79 @@ extern "C" int srlz_plan_cem(const float* states, const float* wf, const float* 
   int* ws_pop = (int*)(ws_ret + (size_t)N * K);
   SRLZ_HIP(hipMemsetAsync(tickets, 0, (size_t)N * 4, as_stream(stream)));  // (a call cut short must not leave the next one a ticket)
   const size_t lds = ro_lds_bytes(S, true) + ((size_t)T * A + 2 * (size_t)K) * 4;
-  SRLZ_MAX_LDS(plan_cem_kernel, lds);
+  SRLZ_MAX_LDS(plan_cem_kernel<PlanArgs>, lds);
   for (int i = 0; i < iterations; ++i) {
     PlanArgs a{{states, wf, bf, w1, b1, w2, b2, w3, b3, nullptr, keep ? returns + (size_t)i * N * K : ws_ret, nullptr, nullptr, T, S, A, H,
                 gamma},
                keep ? plans + (size_t)i * N * K * T : ws_pop, init_weights, init_env_stride, cum, tickets, bestkey, best_plan,
                best_return, K, tiles, i, elites, sharpness, (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32)};
-    SRLZ_LAUNCH(plan_cem_kernel, dim3((unsigned)(N * tiles)), dim3(RO_THREADS), lds, as_stream(stream), a);
+    SRLZ_LAUNCH(plan_cem_kernel<PlanArgs>, dim3((unsigned)(N * tiles)), dim3(RO_THREADS), lds, as_stream(stream), a);
+  }
+  return SRLZ_OK;
+}
+
+// ---- the same planner keyed by the score with the goal term (include/srlz.h states the rule); the reward head is optional ----
+extern "C" int srlz_plan_goal_supported(int S, int A, int H, int n_rewards, int has_reward, int K, int T) {
+  return pl_goal_supported(S, A, H, n_rewards, has_reward, K, T);
+}
+
+extern "C" size_t srlz_plan_goal_workspace(int N, int K, int T, int keep_population) {
+  return srlz_plan_workspace(N, K, T, keep_population);
+}
+
+extern "C" int srlz_plan_cem_goal(const float* states, const float* wf, const float* bf, const float* w1, const float* b1,
+                                  const float* w2, const float* b2, const float* w3, const float* b3, const unsigned* init_weights,
+                                  long long init_env_stride, int* best_plan, float* best_return, unsigned* cum, int* plans,
+                                  float* returns, void* ws, size_t ws_bytes, int N, int K, int T, int S, int A, int H, int n_rewards,
+                                  int iterations, int elites, int sharpness, float gamma, unsigned long long seed, const float* goal,
+                                  long long goal_env_stride, float goal_weight, int goal_mode, srlz_stream_t stream) {
+  const int n_head = (w1 != nullptr) + (b1 != nullptr) + (w2 != nullptr) + (b2 != nullptr) + (w3 != nullptr) + (b3 != nullptr);
+  SRLZ_REQUIRE(n_head == 0 || n_head == 6, SRLZ_ERR_BAD_DESC,
+               "plan_cem_goal: the reward head is given whole (six pointers) or not at all, got %d of them", n_head);
+  const bool reward = n_head == 6;
+  SRLZ_REQUIRE(pl_goal_supported(S, A, H, n_rewards, reward, K, T), SRLZ_ERR_BAD_DESC,
+               "plan_cem_goal: S=%d A=%d H=%d n_rewards=%d K=%d T=%d outside the limits 1 <= S <= %d, 1 <= A <= %d, 1 <= H <= %d, "
+               "n_rewards == 2, 1 <= K <= %d, 1 <= T <= %d", S, A, H, n_rewards, K, T, RO_MAX_S, PL_MAX_A, RO_MAX_H, PL_MAX_K, PL_MAX_T);
+  SRLZ_REQUIRE(pl_rows_ok(N, K), SRLZ_ERR_BAD_DESC, "plan_cem_goal: N=%d K=%d: at least one environment, N * K below 2^31 - %d", N, K,
+               RO_ROWS);
+  SRLZ_REQUIRE(iterations >= 1 && elites >= 1 && elites <= K && sharpness >= 0 && sharpness <= PL_MAX_Q, SRLZ_ERR_BAD_DESC,
+               "plan_cem_goal: iterations=%d (>= 1), elites=%d (1 .. K = %d), sharpness=%d (0 .. %d)", iterations, elites, K, sharpness,
+               PL_MAX_Q);
+  SRLZ_REQUIRE(init_env_stride == 0 || init_env_stride == (long long)T * A, SRLZ_ERR_BAD_DESC,
+               "plan_cem_goal: init_weights are [N,T,A] (environment stride T * A = %lld) or shared [T,A] (stride 0), got stride %lld",
+               (long long)T * A, init_env_stride);
+  SRLZ_REQUIRE((plans != nullptr) == (returns != nullptr), SRLZ_ERR_BAD_DESC,
+               "plan_cem_goal: the population is kept whole (plans and returns) or not at all");
+  SRLZ_REQUIRE(isfinite(goal_weight) && goal_weight > 0.f, SRLZ_ERR_BAD_DESC, "plan_cem_goal: goal_weight=%g must be finite and > 0",
+               (double)goal_weight);
+  SRLZ_REQUIRE(goal_mode == 0 || goal_mode == 1, SRLZ_ERR_BAD_DESC, "plan_cem_goal: goal_mode=%d is neither 0 (running) nor 1 (final)",
+               goal_mode);
+  SRLZ_REQUIRE(goal_env_stride == 0 || goal_env_stride == (long long)S, SRLZ_ERR_BAD_DESC,
+               "plan_cem_goal: goals are [N,S] (environment stride S = %d) or one shared [S] (stride 0), got stride %lld", S,
+               goal_env_stride);
+  const int tiles = (K + RO_ROWS - 1) / RO_ROWS;
+  SRLZ_REQUIRE((long long)N * tiles <= 0x7fffffffLL && (long long)N * K * T * (plans ? iterations : 1) <= (1LL << 40), SRLZ_ERR_BAD_DESC,
+               "plan_cem_goal: N=%d K=%d T=%d iterations=%d: too many workgroups or a population beyond 2^40 actions", N, K, T,
+               iterations);
+  SRLZ_REQUIRE(states && wf && bf && best_plan && best_return && cum && ws && goal, SRLZ_ERR_NULL, "plan_cem_goal: null pointer");
+  const bool keep = plans != nullptr;
+  const size_t need = pl_workspace(N, K, T, keep);
+  SRLZ_REQUIRE(ws_bytes >= need, SRLZ_ERR_WORKSPACE, "plan_cem_goal: workspace of %zu bytes, %zu needed", ws_bytes, need);
+
+  unsigned* tickets = (unsigned*)ws;
+  float* bestkey = (float*)(tickets + N);
+  float* ws_ret = bestkey + N;
+  int* ws_pop = (int*)(ws_ret + (size_t)N * K);
+  SRLZ_HIP(hipMemsetAsync(tickets, 0, (size_t)N * 4, as_stream(stream)));
+  const size_t lds = pl_lds_bytes(S, reward, true, K, T, A);
+  SRLZ_MAX_LDS(plan_cem_kernel<PlanGoalArgs>, lds);
+  for (int i = 0; i < iterations; ++i) {
+    PlanGoalArgs a{{{states, wf, bf, w1, b1, w2, b2, w3, b3, nullptr, keep ? returns + (size_t)i * N * K : ws_ret, nullptr, nullptr, T, S, A,
+                     reward ? H : 0, gamma},
+                    keep ? plans + (size_t)i * N * K * T : ws_pop, init_weights, init_env_stride, cum, tickets, bestkey, best_plan,
+                    best_return, K, tiles, i, elites, sharpness, (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32)},
+                   {goal, goal_env_stride, goal_weight, goal_mode, nullptr}};
+    SRLZ_LAUNCH(plan_cem_kernel<PlanGoalArgs>, dim3((unsigned)(N * tiles)), dim3(RO_THREADS), lds, as_stream(stream), a);
   }
   return SRLZ_OK;
 }

@@ -23,7 +23,10 @@
 // state tile (S = 1024) does not fit next to that, and H = 64 would be a second MFMA block and twice the partial blocks.
 // 166 VGPRs, no scratch (tools/kres.py): three waves a SIMD by registers, one workgroup a CU by LDS at S = 512, three at S = 200.
 // The tile itself (ro_gemm, the step loop, the reward head) is rollout_tile.h, shared with plan.hip; this file is the rows whose
-// actions come from the caller's plans, and the launcher.
+// actions come from the caller's plans, and the launchers.
+// rollout_goal_kernel (srlz_rollout_goal) is the same tile with its goal term compiled in: per step one more reduction over the state
+// tile — |s_{t+1} - goal|^2, 16 partials a row in 2.1 KB of LDS — joins the score; 186 VGPRs, no scratch.  rollout_kernel itself is,
+// instruction for instruction, what it was without that switch.
 #include <math.h>
 #include "common.h"
 #include "rollout_tile.h"
@@ -60,6 +63,13 @@ __global__ __launch_bounds__(RO_THREADS) void rollout_kernel(const RolloutArgs p
   ro_tile(p.tile, ro_lds, rows);
 }
 
+// The same rows with the goal term of the score compiled in (rollout_tile.h, Goal = true).
+__global__ __launch_bounds__(RO_THREADS) void rollout_goal_kernel(const RolloutArgs p, const GoalArgs g) {
+  extern __shared__ __attribute__((aligned(16))) float ro_lds[];
+  PlanRows rows{p, (long long)blockIdx.x * RO_ROWS};
+  ro_tile<PlanRows, true>(p.tile, ro_lds, rows, &g);
+}
+
 }  // namespace
 
 extern "C" int srlz_rollout_supported(int S, int A, int H, int n_rewards) { return ro_supported(S, A, H, n_rewards); }
@@ -91,5 +101,46 @@ extern "C" int srlz_rollout(const float* states, const int* plans, long long pla
   const size_t lds = ro_lds_bytes(S, reward);
   SRLZ_MAX_LDS(rollout_kernel, lds);
   SRLZ_LAUNCH(rollout_kernel, dim3((unsigned)((R + RO_ROWS - 1) / RO_ROWS)), dim3(RO_THREADS), lds, as_stream(stream), a);
+  return SRLZ_OK;
+}
+
+// ---- the same launch with the goal-distance term in the score (include/srlz.h states the rule) ----
+extern "C" int srlz_rollout_goal_supported(int S, int A, int H, int n_rewards, int has_reward) {
+  return ro_goal_supported(S, A, H, n_rewards, has_reward);
+}
+
+extern "C" int srlz_rollout_goal(const float* states, const int* plans, long long plan_env_stride, const float* wf, const float* bf,
+                                 const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
+                                 float* final_states, float* returns, float* trajectory, float* reward_logits, int N, int K, int T,
+                                 int S, int A, int H, int n_rewards, float gamma, const float* goal, long long goal_env_stride,
+                                 float goal_weight, int goal_mode, float* goal_dist, srlz_stream_t stream) {
+  const int n_head = (w1 != nullptr) + (b1 != nullptr) + (w2 != nullptr) + (b2 != nullptr) + (w3 != nullptr) + (b3 != nullptr);
+  SRLZ_REQUIRE(n_head == 0 || n_head == 6, SRLZ_ERR_BAD_DESC,
+               "rollout_goal: the reward head is given whole (six pointers) or not at all, got %d of them", n_head);
+  const bool reward = n_head == 6;
+  SRLZ_REQUIRE(ro_goal_supported(S, A, H, n_rewards, reward), SRLZ_ERR_BAD_DESC,
+               "rollout_goal: S=%d A=%d H=%d n_rewards=%d outside the limits 1 <= S <= %d, 1 <= A <= %d, 1 <= H <= %d, n_rewards == 2",
+               S, A, H, n_rewards, RO_MAX_S, RO_MAX_A, RO_MAX_H);
+  SRLZ_REQUIRE(N >= 1 && K >= 1 && T >= 1 && (long long)N * K <= 0x7fffffffLL - RO_ROWS, SRLZ_ERR_BAD_DESC,
+               "rollout_goal: N=%d K=%d T=%d: at least one row and one step, N * K below 2^31 - %d", N, K, T, RO_ROWS);
+  SRLZ_REQUIRE(plan_env_stride == 0 || plan_env_stride == (long long)K * T, SRLZ_ERR_BAD_DESC,
+               "rollout_goal: plans are [N,K,T] (environment stride K * T = %lld) or shared [K,T] (stride 0), got stride %lld",
+               (long long)K * T, plan_env_stride);
+  SRLZ_REQUIRE(reward || !reward_logits, SRLZ_ERR_BAD_DESC, "rollout_goal: reward_logits asked for without a reward head");
+  SRLZ_REQUIRE(isfinite(goal_weight) && goal_weight > 0.f, SRLZ_ERR_BAD_DESC, "rollout_goal: goal_weight=%g must be finite and > 0",
+               (double)goal_weight);
+  SRLZ_REQUIRE(goal_mode == 0 || goal_mode == 1, SRLZ_ERR_BAD_DESC, "rollout_goal: goal_mode=%d is neither 0 (running) nor 1 (final)",
+               goal_mode);
+  SRLZ_REQUIRE(goal_env_stride == 0 || goal_env_stride == (long long)S, SRLZ_ERR_BAD_DESC,
+               "rollout_goal: goals are [N,S] (environment stride S = %d) or one shared [S] (stride 0), got stride %lld", S,
+               goal_env_stride);
+  SRLZ_REQUIRE(states && plans && wf && bf && final_states && goal, SRLZ_ERR_NULL, "rollout_goal: null pointer");
+  const int R = N * K;
+  RolloutArgs a{{states, wf, bf, w1, b1, w2, b2, w3, b3, final_states, returns, trajectory, reward_logits, T, S, A, reward ? H : 0, gamma},
+                plans, plan_env_stride, R, K};
+  GoalArgs ga{goal, goal_env_stride, goal_weight, goal_mode, goal_dist};
+  const size_t lds = ro_lds_bytes(S, reward, true);
+  SRLZ_MAX_LDS(rollout_goal_kernel, lds);
+  SRLZ_LAUNCH(rollout_goal_kernel, dim3((unsigned)((R + RO_ROWS - 1) / RO_ROWS)), dim3(RO_THREADS), lds, as_stream(stream), a, ga);
   return SRLZ_OK;
 }

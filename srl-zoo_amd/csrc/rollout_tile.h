@@ -17,6 +17,8 @@ constexpr int RO_MAX_A = 65536;
 constexpr int RO_WAVES = 8;
 constexpr int RO_THREADS = 64 * RO_WAVES;
 constexpr int RO_KC = 32;       // k of a chunk: the B-operand loads in flight ahead of its 16 MFMAs
+constexpr int RO_GOAL_Q = RO_THREADS / RO_ROWS;  // partial sums of a row's goal distance: one per column group
+constexpr size_t RO_LDS_CAP = 160 * 1024;        // LDS of a CU
 
 // What the tile reads and writes, whatever the source of its rows.
 struct TileArgs {
@@ -28,17 +30,35 @@ struct TileArgs {
   float gamma;
 };
 
+// The goal term of the score (ro_tile<Rows, true> alone takes one): ret += g * (prob - w * c_t), or g * -(w * c_t) without a reward
+// head.  A kernel argument of its own, so that the kernels without a goal keep the arguments — and the code — they had.
+struct GoalArgs {
+  const float* goal;  // [N,S], or one [S] with stride 0
+  long long stride;   // floats between two environments' goals
+  float w;
+  int final;          // c_t = d_t at every step (0) or at t == T-1 alone (1)
+  float* dist;        // by output row, [T] each; may be NULL
+};
+
 __host__ __device__ inline int ro_sp(int S) { return (S + RO_KC - 1) & ~(RO_KC - 1); }  // the tile's k, whole chunks
 
-// floats of LDS: state tile, 8 partial blocks, h1, h2, W2, W3, b1, b2, b3 (+2 pad), then 2 * 32 ints
-__host__ __device__ inline size_t ro_lds_bytes(int S, bool reward) {
+// floats of LDS: state tile, 8 partial blocks, h1, h2, W2, W3, b1, b2, b3 (+2 pad), the goal distance's 16 partials a row, then
+// 2 * 32 ints
+__host__ __device__ inline size_t ro_lds_bytes(int S, bool reward, bool goal = false) {
   size_t fl = (size_t)ro_sp(S) * RO_LD;
   if (reward) fl += RO_WAVES * RO_ROWS * RO_LD + 2 * RO_ROWS * RO_LD + RO_MAX_H * RO_MAX_H + 2 * RO_MAX_H + 2 * RO_MAX_H + 4;
+  if (goal) fl += RO_GOAL_Q * RO_LD;
   return (fl + 2 * RO_ROWS) * 4;
 }
 
 inline int ro_supported(int S, int A, int H, int n_rewards) {
   return S >= 1 && S <= RO_MAX_S && A >= 1 && A <= RO_MAX_A && H >= 1 && H <= RO_MAX_H && n_rewards == 2;
+}
+
+// With the goal term (srlz_rollout_goal_supported is this; the planner adds its own LDS on top): the head's limits — none without a
+// head — and the tile with the goal's partials inside the CU's LDS.
+inline int ro_goal_supported(int S, int A, int H, int n_rewards, int has_reward) {
+  return ro_supported(S, A, has_reward ? H : 1, has_reward ? n_rewards : 2) && ro_lds_bytes(S, has_reward != 0, true) <= RO_LDS_CAP;
 }
 
 // acc += st[32 x k-range] . W[j][koff + k]^T over the chunks c0, c0 + cstep, .. of 32 k each.  w (uniform) + woff (this lane's row
@@ -92,6 +112,27 @@ __device__ __forceinline__ void ro_gemm(f32x16& acc, const float* st, const floa
 
 __device__ __forceinline__ float ro_relu(float v) { return v < 0.f ? 0.f : v; }  // NaN stays NaN
 
+// One step of the score with the goal term, as include/srlz.h states it: fl(w * c), fl(prob - .), fl(g * term), fl(ret + .), fl(g * gamma),
+// each rounded on its own.  Plain operators under contract(off): the __fmul_rn / __fadd_rn of this toolchain are plain operators that
+// the default contraction mode fuses into one FMA (as it does in the reward branch's ret + g * prob, whose bits stand as they are).
+__device__ __forceinline__ void ro_goal_step(float& ret, float& g, float prob, bool reward, float w, float c, float gamma) {
+#pragma clang fp contract(off)
+  const float wc = w * c;
+  const float term = reward ? prob - wc : -wc;
+  const float gt = g * term;
+  ret = ret + gt;
+  g = g * gamma;
+}
+
+// A row's squared distance to its goal: 16 partial sums, each an fma chain over its columns in ascending order, added in group order.
+__device__ __forceinline__ float ro_goal_sum(const float* gq, int row) {
+#pragma clang fp contract(off)
+  float d = gq[row];
+#pragma unroll
+  for (int q = 1; q < RO_GOAL_Q; ++q) d = d + gq[q * RO_LD + row];
+  return d;
+}
+
 // The tile for all T steps.  `lds`: ro_lds_bytes(S, reward) bytes, 16-byte aligned.  Rows: a row source with
 //   bool exists(int i)          row i of the tile is a row of the call (asked by any thread)
 //   long long env(int i)        the row of p.states row i starts from (an existing row)
@@ -99,9 +140,12 @@ __device__ __forceinline__ float ro_relu(float v) { return v < 0.f ? 0.f : v; } 
 //   void begin(int i)           called once by thread i < 32 of an existing row, before its first action is asked for
 //   int action(int i, int t)    row i's action at step t: asked once per step, in step order, by thread i < 32 alone and only
 //                               for an existing row — one step ahead of the step that uses it
+// Goal (compile time): the goal-distance term of include/srlz.h joins the score; gp is then given and `lds` is
+// ro_lds_bytes(S, reward, true) bytes.
+// Without it not one instruction of the goal term exists.
 // Ends behind a workgroup barrier: every output of the tile has been issued by its thread.
-template <class Rows>
-__device__ __forceinline__ void ro_tile(const TileArgs& p, float* lds, Rows& rows) {
+template <class Rows, bool Goal = false>
+__device__ __forceinline__ void ro_tile(const TileArgs& p, float* lds, Rows& rows, const GoalArgs* gp = nullptr) {
   const int S = p.S, A = p.A, H = p.H, T = p.T;
   const bool reward = p.w1 != nullptr;
   const int sp = ro_sp(S), nblk = (S + 31) >> 5;
@@ -118,6 +162,8 @@ __device__ __forceinline__ void ro_tile(const TileArgs& p, float* lds, Rows& row
     b2s = fp; fp += RO_MAX_H;
     b3s = fp; fp += 4;
   }
+  float* gq = nullptr;  // the goal distance's partials: gq[q * RO_LD + row]
+  if constexpr (Goal) { gq = fp; fp += RO_GOAL_Q * RO_LD; }
   int* act = (int*)fp;        // this step's action of each row, -1 = outside [0, A)
   int* bad = act + RO_ROWS;   // sticky: the row met an action outside [0, A)
 
@@ -209,6 +255,21 @@ __device__ __forceinline__ void ro_tile(const TileArgs& p, float* lds, Rows& row
     }
     __syncthreads();  // s_{t+1} is in the tile
 
+    // ---- goal distance: thread (row i, column group q) sums fl(s_{t+1}[j] - goal[j])^2 over j = q, q + 16, .. in ascending order ----
+    if constexpr (Goal) {
+      const int i = tid & 31, q = tid >> 5;
+      float part = 0.f;
+      if (rows.exists(i)) {  // (a tile may straddle environments: each row reads its own environment's goal)
+        const float* gl = gp->goal + rows.env(i) * gp->stride;
+        for (int j = q; j < S; j += RO_GOAL_Q) {
+          const float e = __fsub_rn(st[j * RO_LD + i], gl[j]);
+          part = fmaf(e, e, part);
+        }
+      }
+      gq[q * RO_LD + i] = part;
+      if (!reward) __syncthreads();  // (with a reward head its barriers stand between these writes and the row's sum)
+    }
+
     // ---- s_{t+1} out: wave w writes rows 4w .. 4w+3 of the tile, a row's S floats along the lanes ----
     if (p.trajectory || (t == T - 1 && p.final_states)) {
       for (int i = wave * (RO_ROWS / RO_WAVES); i < (wave + 1) * (RO_ROWS / RO_WAVES); ++i) {
@@ -252,6 +313,7 @@ __device__ __forceinline__ void ro_tile(const TileArgs& p, float* lds, Rows& row
       __syncthreads();
     }
     if (tid < RO_ROWS) {
+      [[maybe_unused]] float pgoal = 0.f;  // (Goal) this step's prob, kept for the goal step below
       if (reward) {
         float l0 = 0.f, l1 = 0.f;
         for (int m = 0; m < H; ++m) {
@@ -263,8 +325,12 @@ __device__ __forceinline__ void ro_tile(const TileArgs& p, float* lds, Rows& row
         l1 = __fadd_rn(l1, b3s[1]);
         if (bad[tid]) l0 = l1 = nanf_;
         const float prob = 1.f / (1.f + expf(l0 - l1));
-        ret = __fadd_rn(ret, __fmul_rn(g, prob));
-        g = __fmul_rn(g, p.gamma);
+        if constexpr (Goal) {
+          pgoal = prob;
+        } else {
+          ret = __fadd_rn(ret, __fmul_rn(g, prob));
+          g = __fmul_rn(g, p.gamma);
+        }
         if (mine) {
           const long long rg = rows.out(tid);
           if (p.logits) {
@@ -272,6 +338,15 @@ __device__ __forceinline__ void ro_tile(const TileArgs& p, float* lds, Rows& row
             o[0] = l0;
             o[1] = l1;
           }
+          if (!Goal && t == T - 1 && p.returns) p.returns[rg] = ret;
+        }
+      }
+      if constexpr (Goal) {
+        const float d = ro_goal_sum(gq, tid);
+        ro_goal_step(ret, g, pgoal, reward, gp->w, (!gp->final || t == T - 1) ? d : 0.f, p.gamma);
+        if (mine) {
+          const long long rg = rows.out(tid);
+          if (gp->dist) gp->dist[rg * T + t] = d;
           if (t == T - 1 && p.returns) p.returns[rg] = ret;
         }
       }

@@ -279,6 +279,13 @@ _PROTOS = {
     "srlz_plan_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
     "srlz_plan_cem": (c_int, [P, P, P, P, P, P, P, P, P, P, c_longlong, P, P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int,
                               c_int, c_int, c_int, c_int, c_int, c_float, c_ulonglong, P]),
+    "srlz_rollout_goal_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "srlz_rollout_goal": (c_int, [P, P, c_longlong, P, P, P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                  c_float, P, c_longlong, c_float, c_int, P, P]),
+    "srlz_plan_goal_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "srlz_plan_goal_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "srlz_plan_cem_goal": (c_int, [P, P, P, P, P, P, P, P, P, P, c_longlong, P, P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int,
+                                   c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_ulonglong, P, c_longlong, c_float, c_int, P]),
 }
 
 # entry points whose int return value is data, not a status
@@ -292,7 +299,7 @@ _NOT_STATUS = {"srlz_version", "srlz_device_cus", "srlz_conv64_fwd_tiles", "srlz
                "srlz_dense_out_fwd_loss_workgroups", "srlz_reward_probe_chunk_rows", "srlz_infer_block_supported",
                "srlz_infer_tile", "srlz_conv64_bwd_fused_workgroups", "srlz_conv1_workgroups",
                "srlz_conv1_buffer_staging_supported", "srlz_infer_dec_supported", "srlz_infer_dec_tile", "srlz_rollout_supported",
-               "srlz_rollout_tile", "srlz_plan_supported"}
+               "srlz_rollout_tile", "srlz_plan_supported", "srlz_rollout_goal_supported", "srlz_plan_goal_supported"}
 
 EXPORTED = sorted(_PROTOS.keys())
 

@@ -594,6 +594,21 @@ def reconstruct(encoder, decoder, frames):
 # buffers are made on the first plan call and grown only when a call asks for more; what a call returns are views of them, valid
 # until the next call (shifted() is a new tensor).  Device init_weights — a Plan's shifted() — are taken as they are; host ones are
 # checked: non-negative, every row with a positive total.
+#
+# Goals.  "Drive the learned state to the state of this goal picture":
+#     out = dyn.rollout(states, plans, gamma=1.0, goal=g, goal_weight=1.0, goal_mode="running", keep_goal_dist=False)
+#     out.returns, out.best, out.goal_dist            # the score [N,K], its argmax [N], |s_{t+1} - goal|^2 [N,K,T]
+#     a = dyn.act(states, plans, goal=g, goal_mode="final")
+#     p = dyn.plan(states, horizon, ..., goal=g, goal_weight=1.0, goal_mode="running")   # p.best_return, p.returns are scores
+#     p = reach(encoder, dyn, frames, goal_frames, horizon, **plan_kwargs)               # from camera frames, on the device
+# goal: floating point [S] (shared, read with a stride of 0) or [N,S], numpy or a device tensor.  Per step (include/srlz.h):
+#     d_t = |s_{t+1} - goal|^2;  c_t = d_t ("running") | d_t at the last step alone ("final");  term_t = prob_t - w c_t, or -w c_t
+#     without a reward head;  score = sum_t g_t term_t
+# With a goal only the forward head is required: a reward head the losses trained joins the score, an untrained one only under
+# untrained_ok.  Route "rollout" is srlz_rollout_goal / srlz_plan_cem_goal — the same tile with its goal term compiled in, the same
+# bits for the states and logits — where goal_route_for / plan_goal_route_for say so and within max_rows / max_horizon; otherwise
+# route "model": the model's own forwardModel / rewardModel step by step, scored by goal_scores (the rule written once, numpy or
+# torch), which also feeds cem_host.  A call without a goal takes exactly the path it always took.
 # =============================================================================================================
 ROUTE_ROLLOUT = "rollout"
 HEADS = ("forward", "inverse", "reward")
@@ -601,10 +616,11 @@ HEADS = ("forward", "inverse", "reward")
 
 class Rollout(object):
     """What LatentDynamics.rollout returns; a field the call did not ask for (or has no head for) is None."""
-    __slots__ = ("final_states", "returns", "trajectory", "reward_logits", "best")
+    __slots__ = ("final_states", "returns", "trajectory", "reward_logits", "best", "goal_dist")
 
-    def __init__(self, final_states, returns=None, trajectory=None, reward_logits=None, best=None):
+    def __init__(self, final_states, returns=None, trajectory=None, reward_logits=None, best=None, goal_dist=None):
         self.final_states, self.returns, self.trajectory, self.reward_logits, self.best = final_states, returns, trajectory, reward_logits, best
+        self.goal_dist = goal_dist
 
 
 def _dynamics_owner(model):
@@ -673,6 +689,75 @@ def check_plans(plans, n, n_actions):
         if lo < 0 or hi >= n_actions:
             raise ValueError("plans must hold actions in [0, %d), got %d .. %d" % (n_actions, lo, hi))
     return (shape[-2] if len(shape) > 1 else 1), shape[-1], len(shape) < 3, len(shape) == 1
+
+
+# ---- goals: "drive the learned state to the state of this goal picture" (include/srlz.h states the scoring rule) ----
+GOAL_MODES = ("running", "final")
+
+
+def check_goal(goal, n, state_dim):
+    """Validate a call's goal: floating point, one [S] shared by every environment or [N,S] with N = n, S = state_dim.
+    Returns shared: whether one goal serves every environment."""
+    if not isinstance(goal, (np.ndarray, torch.Tensor)):
+        raise ValueError("goal must be a numpy array or a torch tensor, got %s" % type(goal).__name__)
+    is_float = np.issubdtype(goal.dtype, np.floating) if isinstance(goal, np.ndarray) else goal.dtype.is_floating_point
+    if not is_float:
+        raise ValueError("goal must be floating point (got %s)" % (goal.dtype,))
+    shape = tuple(goal.shape)
+    if len(shape) not in (1, 2):
+        raise ValueError("goal must be [N,S] or [S], got shape %s" % (shape,))
+    if shape[-1] != state_dim:
+        raise ValueError("goal of shape %s is %d wide, the dynamics take state_dim = %d" % (shape, shape[-1], state_dim))
+    if len(shape) == 2 and shape[0] != n:
+        raise ValueError("goal of shape %s is for %d environments, the call has %d states" % (shape, shape[0], n))
+    return len(shape) == 1
+
+
+def check_goal_args(goal_weight, goal_mode):
+    """Validate a goal's weight (a finite number > 0) and mode ("running" or "final").  Returns (float weight, mode)."""
+    if isinstance(goal_weight, bool) or not isinstance(goal_weight, (int, float, np.integer, np.floating)):
+        raise ValueError("goal_weight must be a number, got %r" % (goal_weight,))
+    w = float(goal_weight)
+    with np.errstate(over="ignore", under="ignore"):
+        w32 = float(np.float32(w))  # what the kernel takes
+    if not np.isfinite(w32) or not w32 > 0:
+        raise ValueError("goal_weight must be finite and > 0 (as a float32), got %r" % (goal_weight,))
+    if goal_mode not in GOAL_MODES:
+        raise ValueError("goal_mode must be 'running' or 'final', got %r" % (goal_mode,))
+    return w, goal_mode
+
+
+def goal_scores(trajectory, goal, probs=None, gamma=1.0, goal_weight=1.0, goal_mode="running"):
+    """The scoring rule of include/srlz.h on a whole trajectory, in the trajectory's own arithmetic (numpy or torch, any float type):
+    trajectory [N,K,T,S] (entry t = s_{t+1}), goal [S] or [N,S], probs [N,K,T] = softmax(reward logits)[1] or None (no reward head).
+        d_t = |s_{t+1} - goal|^2;  c_t = d_t (running) | d_t at t = T-1 alone (final);  term_t = probs_t - w c_t  |  -w c_t
+        score = sum_t g_t term_t,  g_0 = 1, g_{t+1} = g_t * gamma (gamma as the float32 the kernel takes)
+    Returns (scores [N,K], goal_dist [N,K,T]).  What route "model" and the host planner score by; the kernels' order of d_t's sum
+    differs, their score's order is this one."""
+    w, goal_mode = check_goal_args(goal_weight, goal_mode)
+    if torch.is_tensor(trajectory):
+        g = torch.as_tensor(goal).to(trajectory.device, trajectory.dtype)
+        scalar = lambda v: torch.tensor(float(np.float32(v)), dtype=trajectory.dtype, device=trajectory.device)
+    else:
+        trajectory = np.asarray(trajectory)
+        g = np.asarray(goal.detach().cpu().numpy() if torch.is_tensor(goal) else goal).astype(trajectory.dtype)
+        scalar = lambda v: trajectory.dtype.type(np.float32(v))
+    g = g.reshape((1, 1, 1, -1)) if g.ndim == 1 else g.reshape((g.shape[0], 1, 1, g.shape[1]))
+    diff = trajectory - g
+    dist = (diff * diff).sum(-1)
+    t = dist.shape[-1]
+    wv, gam, disc = scalar(w), scalar(gamma), scalar(1.0)
+    score = torch.zeros_like(dist[..., 0]) if torch.is_tensor(dist) else np.zeros_like(dist[..., 0])
+    for step in range(t):
+        term = None
+        if goal_mode == "running" or step == t - 1:
+            term = -(wv * dist[..., step]) if probs is None else probs[..., step] - wv * dist[..., step]
+        elif probs is not None:
+            term = probs[..., step]
+        if term is not None:  # (final mode without a reward head: the steps before the last add -0)
+            score = score + disc * term
+        disc = disc * gam
+    return score, dist
 
 
 # ---- the planner's host side: argument checks, the route table and the same algorithm in numpy (route "model") ----
@@ -747,6 +832,25 @@ def plan_route_for(model, n_plans, horizon, n_envs=1, max_rows=8192):
         return ROUTE_MODEL
     s, a, h, nr = dynamics_dims(model)
     return ROUTE_ROLLOUT if ops.plan_supported(s, a, h, nr, n_plans, horizon) else ROUTE_MODEL
+
+
+def goal_route_for(model, has_goal_only=False):
+    """The route a LatentDynamics of `model` takes for calls with a goal within max_rows and max_horizon (host only: no GPU is asked
+    for).  has_goal_only: the reward head stays out of the score (never trained, or not the reference's three-layer head)."""
+    from models.modules import SRLModules
+    owner = _dynamics_owner(model)
+    s, a, h, nr = dynamics_dims(model)
+    ok = isinstance(owner, SRLModules) and a >= 1 and owner.forward_net.bias is not None and \
+        ops.rollout_goal_supported(s, a, h, nr, not has_goal_only)
+    return ROUTE_ROLLOUT if ok else ROUTE_MODEL
+
+
+def plan_goal_route_for(model, has_goal_only, n_plans, horizon, n_envs=1, max_rows=8192):
+    """The route LatentDynamics.plan takes for a call of n_envs states with a goal (host only: no GPU is asked for)."""
+    if goal_route_for(model, has_goal_only) != ROUTE_ROLLOUT or n_envs * n_plans > max_rows:
+        return ROUTE_MODEL
+    s, a, h, nr = dynamics_dims(model)
+    return ROUTE_ROLLOUT if ops.plan_goal_supported(s, a, h, nr, not has_goal_only, n_plans, horizon) else ROUTE_MODEL
 
 
 def philox4x32_10(counter, key):
@@ -841,6 +945,8 @@ class LatentDynamics(object):
         self.max_rows, self.max_horizon = int(max_rows), int(max_horizon)
         self._route, self.last_route = picked, None
         self._plan_bufs = {}  # the planner's device buffers: made by the first plan call
+        self._goal_bufs = {}  # the goal calls' device buffers: made by the first call with a goal
+        self._forced_model = route is not None
         self.device = next(self.owner.forward_net.parameters()).device
         if self.device.type != "cuda":
             raise C.SrlzError("LatentDynamics: the model must live on the GPU (there is no CPU path)")
@@ -971,6 +1077,89 @@ class LatentDynamics(object):
                     reward_logits=logits, gamma=gamma)
         return final, returns, traj, logits, pl, single, bare
 
+    # ---- calls with a goal (a call without one never comes here) ----
+    def _goal_reward(self):
+        """Whether the reward head joins a goal call's score: a trained one does, an untrained one only under untrained_ok."""
+        return self._uses_reward()
+
+    def _goal_kernel_ok(self, reward):
+        return not self._forced_model and goal_route_for(self.owner, not reward) == ROUTE_ROLLOUT
+
+    def _goal_buffers(self, n):
+        """The staging buffers of a "rollout" call with a goal: the constructor's when it made them (a goal-only call can take the
+        kernel where the reward head's shape refused it), the goal and goal_dist buffers; made once, grown never (n <= max_rows)."""
+        r, t, s, dev = self.max_rows, self.max_horizon, self.state_dim, self.device
+        if not hasattr(self, "_states"):
+            self._states = torch.empty((r, s), dtype=torch.float32, device=dev)
+            self._pin_states = torch.empty((r, s), dtype=torch.float32).pin_memory()
+            self._plans = torch.empty(r * t, dtype=torch.int32, device=dev)
+            self._pin_plans = torch.empty(r * t, dtype=torch.int32).pin_memory()
+            self._final = torch.empty(r * s, dtype=torch.float32, device=dev)
+            self._returns = torch.empty(r, dtype=torch.float32, device=dev)
+            self._traj = torch.empty(r * t * s, dtype=torch.float32, device=dev)
+            self._logits = torch.empty(r * t * 2, dtype=torch.float32, device=dev)
+        b = self._goal_bufs
+        if not b:
+            b["goal"] = torch.empty((r, s), dtype=torch.float32, device=dev)
+            b["dist"] = torch.empty(r * t, dtype=torch.float32, device=dev)
+        return b
+
+    def _device_goal(self, goal, shared, n, staged):
+        """The call's goal as a contiguous fp32 device tensor [S] or [n,S]: the caller's own when it already is one, else a copy (into
+        the goal buffer when staged)."""
+        if isinstance(goal, np.ndarray):
+            goal = torch.from_numpy(np.ascontiguousarray(goal))
+        goal = goal.detach()
+        if goal.device.type == "cuda" and goal.is_contiguous() and goal.dtype == torch.float32:
+            return goal
+        if not staged:
+            return goal.to(self.device, torch.float32).contiguous()
+        dst = self._goal_bufs["goal"][0] if shared else self._goal_bufs["goal"][:n]
+        dst.copy_(goal, non_blocking=True)
+        return dst
+
+    def _model_rollout_goal(self, states, plans, goal, gamma, weight, mode, reward, keep_logits):
+        """Route "model" with a goal: the owner's own forwardModel and rewardModel step by step, scored by goal_scores."""
+        final, _, traj, logits = self._model_rollout(states, plans, gamma, False, True, False)
+        n, k, t, s = traj.shape
+        probs = lg = None
+        if reward:
+            with torch.no_grad():
+                prev = torch.cat((states.view(n, 1, 1, s).expand(n, k, 1, s), traj[:, :, :-1]), dim=2).reshape(-1, s)
+                lg = self.owner.rewardModel(prev, traj.reshape(-1, s)).view(n, k, t, 2)
+                probs = torch.softmax(lg, dim=-1)[..., 1]
+        scores, dist = goal_scores(traj, goal, probs, gamma, weight, mode)
+        return final, scores, traj, (lg if keep_logits else None), dist
+
+    def _run_goal(self, states, plans, goal, gamma, weight, mode, reward, keep_trajectory, keep_logits, keep_dist):
+        """Both routes on checked inputs, with a goal -> (final [n,k,S], scores [n,k], trajectory | None, logits | None,
+        goal_dist | None, plans on the device, single, bare)."""
+        n, single = check_states(states, self.state_dim)
+        k, t, shared, bare = check_plans(plans, n, self.n_actions)
+        goal_shared = check_goal(goal, n, self.state_dim)
+        shape = (k, t) if shared else (n, k, t)
+        staged = self._goal_kernel_ok(reward) and n * k <= self.max_rows and t <= self.max_horizon
+        self.last_route = ROUTE_ROLLOUT if staged else ROUTE_MODEL
+        if staged:
+            b = self._goal_buffers(n)
+        x = self._device_states(states, n, single, staged)
+        pl = self._device_plans(plans, shape, staged)
+        gl = self._device_goal(goal, goal_shared, n, staged)
+        if not staged:
+            final, scores, traj, logits, dist = self._model_rollout_goal(x, pl, gl, gamma, weight, mode, reward, keep_logits)
+            return final, scores, (traj if keep_trajectory else None), logits, (dist if keep_dist else None), pl, single, bare
+        s, o = self.state_dim, self.owner
+        final = self._final[:n * k * s].view(n, k, s)
+        scores = self._returns[:n * k].view(n, k)
+        traj = self._traj[:n * k * t * s].view(n, k, t, s) if keep_trajectory else None
+        logits = self._logits[:n * k * t * 2].view(n, k, t, 2) if keep_logits else None
+        dist = b["dist"][:n * k * t].view(n, k, t) if keep_dist else None
+        rn = o.reward_net
+        head = (rn[0].weight, rn[0].bias, rn[2].weight, rn[2].bias, rn[4].weight, rn[4].bias) if reward else None
+        ops.rollout_goal(x, pl, o.forward_net.weight, o.forward_net.bias, gl, reward=head, final=final, returns=scores, trajectory=traj,
+                         reward_logits=logits, goal_dist=dist, gamma=gamma, goal_weight=weight, goal_mode=mode)
+        return final, scores, traj, logits, dist, pl, single, bare
+
     @staticmethod
     def _best(returns):
         """argmax_k of returns [n,k], ties to the lowest k (torch.argmax returns the first maximal value); a NaN return is never
@@ -986,11 +1175,22 @@ class LatentDynamics(object):
             x = x.squeeze(k_axis)
         return x[0] if single else x
 
-    def rollout(self, states, plans, gamma=1.0, keep_trajectory=False, keep_logits=False):
+    def rollout(self, states, plans, gamma=1.0, keep_trajectory=False, keep_logits=False, goal=None, goal_weight=1.0,
+                goal_mode="running", keep_goal_dist=False):
         self._need("forward")
         reward = self._uses_reward()
         if keep_logits and not reward:
             self._need("reward")
+        if goal is not None:  # returns is the score (include/srlz.h), with or without a reward head
+            w, mode = check_goal_args(goal_weight, goal_mode)
+            final, scores, traj, logits, dist, _, single, bare = self._run_goal(states, plans, goal, float(gamma), w, mode, reward,
+                                                                                keep_trajectory, keep_logits, keep_goal_dist)
+            best = self._best(scores)
+            d = self._drop
+            return Rollout(d(final, single, bare), d(scores, single, bare), d(traj, single, bare), d(logits, single, bare),
+                           best[0] if single else best, d(dist, single, bare))
+        if keep_goal_dist:
+            raise ValueError("keep_goal_dist needs a goal")
         final, returns, traj, logits, _, single, bare = self._run(states, plans, float(gamma), reward, keep_trajectory, keep_logits)
         best = self._best(returns) if reward else None
         d = self._drop
@@ -1008,11 +1208,17 @@ class LatentDynamics(object):
         final = self._run(states, actions.reshape(n, 1, 1), 1.0, False, False, False)[0]
         return final[0, 0] if single else final[:, 0]
 
-    def act(self, states, plans):
-        """First action of each environment's best plan: [N] int64 ([] for one bare state), computed on the device."""
+    def act(self, states, plans, goal=None, goal_weight=1.0, goal_mode="running"):
+        """First action of each environment's best plan: [N] int64 ([] for one bare state), computed on the device.  With a goal the
+        plans are ranked by the score and only the forward head is required."""
         self._need("forward")
-        self._need("reward")
-        _, returns, _, _, pl, single, _ = self._run(states, plans, 1.0, True, False, False)
+        if goal is not None:
+            w, mode = check_goal_args(goal_weight, goal_mode)
+            _, returns, _, _, _, pl, single, _ = self._run_goal(states, plans, goal, 1.0, w, mode, self._goal_reward(), False, False,
+                                                                False)
+        else:
+            self._need("reward")
+            _, returns, _, _, pl, single, _ = self._run(states, plans, 1.0, True, False, False)
         best = self._best(returns)
         first = pl[..., 0].to(torch.int64)  # [n,k] or (shared) [k]
         a = first[best] if first.dim() == 1 else first.gather(1, best.unsqueeze(1)).squeeze(1)
@@ -1032,20 +1238,32 @@ class LatentDynamics(object):
         return have
 
     def plan(self, states, horizon, n_plans=64, iterations=4, elites=8, sharpness=8, gamma=1.0, seed=0, init_weights=None,
-             keep_population=False):
-        """A categorical cross-entropy search for each environment's action sequence (the comment block above states it) -> Plan."""
+             keep_population=False, goal=None, goal_weight=1.0, goal_mode="running"):
+        """A categorical cross-entropy search for each environment's action sequence (the comment block above states it) -> Plan.
+        With a goal the plans are keyed by the score (best_return and returns are scores) and only the forward head is required."""
         self._need("forward")
-        self._need("reward")
+        if goal is None:
+            self._need("reward")
         n, single = check_states(states, self.state_dim)
         t, k, it, e, q, seed = check_plan_args(horizon, n_plans, iterations, elites, sharpness, seed)
         init_weights, shared = check_init_weights(init_weights, n, t, self.n_actions)
         a = self.n_actions
-        kernel = self._route == ROUTE_ROLLOUT and n * k <= self.max_rows and \
-            ops.plan_supported(self.state_dim, a, self._h, self._nr, k, t)
+        if goal is None:
+            kernel = self._route == ROUTE_ROLLOUT and n * k <= self.max_rows and \
+                ops.plan_supported(self.state_dim, a, self._h, self._nr, k, t)
+        else:
+            goal_shared = check_goal(goal, n, self.state_dim)
+            gw, gmode = check_goal_args(goal_weight, goal_mode)
+            reward = self._goal_reward()
+            kernel = self._goal_kernel_ok(reward) and n * k <= self.max_rows and \
+                ops.plan_goal_supported(self.state_dim, a, self._h, self._nr, reward, k, t)
         if not kernel:
             host_w = init_weights.cpu().numpy() if torch.is_tensor(init_weights) else init_weights
 
             def returns_fn(pl):
+                if goal is not None:
+                    return self._run_goal(states, pl[0] if single else pl, goal, float(gamma), gw, gmode, reward, False, False,
+                                          False)[1].reshape(n, k).float().cpu().numpy()
                 return self._run(states, pl[0] if single else pl, float(gamma), True, False, False)[1].reshape(n, k).cpu().numpy()
             out = cem_host(returns_fn, n, k, t, a, it, e, q, seed, host_w, keep_population)
             self.last_route = ROUTE_MODEL
@@ -1057,6 +1275,9 @@ class LatentDynamics(object):
             returns = torch.from_numpy(out["returns"]).to(dev) if keep_population else None
         else:
             self.last_route = ROUTE_ROLLOUT
+            if goal is not None:
+                self._goal_buffers(n)
+                gl = self._device_goal(goal, goal_shared, n, True)
             x = self._device_states(states, n, single, True)
             b = self._plan_buffers(n, k, t, it, keep_population)
             iw = None
@@ -1070,9 +1291,15 @@ class LatentDynamics(object):
             plans = b["pop"][:it * n * k * t].view(it, n, k, t) if keep_population else None
             returns = b["pret"][:it * n * k].view(it, n, k) if keep_population else None
             o, rn = self.owner, self.owner.reward_net
-            head = (rn[0].weight, rn[0].bias, rn[2].weight, rn[2].bias, rn[4].weight, rn[4].bias)
-            ops.plan_cem(x, o.forward_net.weight, o.forward_net.bias, head, k, t, it, e, q, best_plan, best_return, cum, b["ws"],
-                         gamma=gamma, seed=seed, init_weights=iw, plans=plans, returns=returns)
+            if goal is None or reward:
+                head = (rn[0].weight, rn[0].bias, rn[2].weight, rn[2].bias, rn[4].weight, rn[4].bias)
+            if goal is None:
+                ops.plan_cem(x, o.forward_net.weight, o.forward_net.bias, head, k, t, it, e, q, best_plan, best_return, cum, b["ws"],
+                             gamma=gamma, seed=seed, init_weights=iw, plans=plans, returns=returns)
+            else:
+                ops.plan_cem_goal(x, o.forward_net.weight, o.forward_net.bias, head if reward else None, gl, k, t, it, e, q, best_plan,
+                                  best_return, cum, b["ws"], gamma=gamma, seed=seed, init_weights=iw, plans=plans, returns=returns,
+                                  goal_weight=gw, goal_mode=gmode)
             weights = b["w"][:n * t * a].view(n, t, a)  # (the table's uint32 stay below 2^31 at these limits)
             weights[:, :, :1].copy_(cum[:, :, :1])
             if a > 1:
@@ -1123,3 +1350,25 @@ def imagine(dynamics, decoder, states, plans):
             frames = torch.empty((rows.shape[0],) + tuple(part.shape[1:]), dtype=part.dtype, device=part.device)
         frames[lo:lo + part.shape[0]].copy_(part)
     return frames.view(tuple(traj.shape[:-1]) + tuple(frames.shape[1:]))
+
+
+def reach(encoder, dynamics, frames, goal_frames, horizon, **plan_kwargs):
+    """Plan from camera frames towards goal pictures: dynamics.plan(encoder(frames), horizon, goal=encoder(goal_frames), ...) -> Plan,
+    the states never leaving the device.  frames and goal_frames of the same shape ([N, ...] or one bare frame each); when both fit
+    the encoder's max_batch they go through it as ONE call, otherwise as two."""
+    n, single = check_frames(frames, encoder.frame_layout, encoder.channels, encoder.frame_size)
+    if check_frames(goal_frames, encoder.frame_layout, encoder.channels, encoder.frame_size) != (n, single):
+        raise ValueError("frames and goal_frames must have the same shape, got %s and %s" % (tuple(frames.shape), tuple(goal_frames.shape)))
+    if "goal" in plan_kwargs:
+        raise ValueError("reach takes the goal as goal_frames")
+    # Host frames are uploaded here, with a copy that has ended when it returns: the encoder's pinned staging buffer is refilled by
+    # the host at every call, and two calls back to back would refill it while the first call's copy to the device may still wait
+    # on the stream.  A device tensor is read by the encoder in place.
+    dev = [(torch.from_numpy(np.ascontiguousarray(f)) if isinstance(f, np.ndarray) else f).to(encoder.device) for f in (frames, goal_frames)]
+    if 2 * n <= encoder.max_batch:
+        both = encoder(torch.cat([f.unsqueeze(0) if single else f for f in dev], dim=0))
+        states, goals = (both[0], both[1]) if single else (both[:n], both[n:])
+    else:
+        states = encoder(dev[0].contiguous()).clone()  # (the encoder's state buffer is reused by the next call)
+        goals = encoder(dev[1].contiguous())
+    return dynamics.plan(states, horizon, goal=goals, **plan_kwargs)

@@ -2346,3 +2346,112 @@ def plan_cem(states, wf, bf, reward, n_plans, horizon, iterations, elites, sharp
                ptr(cum), ptr(plans), ptr(returns), ptr(workspace), workspace.numel(), n, k, t, s, a, h, 2, it, int(elites),
                int(sharpness), float(gamma), int(seed) & 0xFFFFFFFFFFFFFFFF, stream())
     return best_plan
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# Goal-distance scores (csrc/rollout_tile.h with its goal term compiled in): the rollout and the planner above scored by
+# prob_t - w * |s_{t+1} - goal|^2, or by -w * |s_{t+1} - goal|^2 alone without a reward head (include/srlz.h states the rule).  Thin, as
+# rollout and plan_cem: the caller owns every buffer.
+# ----------------------------------------------------------------------------------------------------------------
+GOAL_MODES = {"running": 0, "final": 1}
+
+
+def rollout_goal_supported(s, a, h=16, n_rewards=2, has_reward=True):
+    return bool(C.rollout_goal_supported(int(s), int(a), int(h), int(n_rewards), int(bool(has_reward))))
+
+
+def plan_goal_supported(s, a, h, n_rewards, has_reward, n_plans, horizon):
+    return bool(C.plan_goal_supported(int(s), int(a), int(h), int(n_rewards), int(bool(has_reward)), int(n_plans), int(horizon)))
+
+
+def plan_goal_workspace(n, n_plans, horizon, keep_population=False):
+    """Bytes of workspace of a plan_cem_goal call; 0 for a shape it refuses."""
+    return int(C.plan_goal_workspace(int(n), int(n_plans), int(horizon), int(bool(keep_population))))
+
+
+def _goal_args(goal, n, s, goal_mode, who):
+    """(goal tensor, environment stride, mode as the C ABI's int) of a goal fp32 [S] (shared, stride 0) or [N,S]."""
+    goal = _rollout_f32(goal, "goal")
+    if goal is None or tuple(goal.shape) not in ((s,), (n, s)):
+        raise C.SrlzError("%s: goal must be [S] = %s or [N,S] = %s, got %s"
+                          % (who, (s,), (n, s), None if goal is None else tuple(goal.shape)))
+    if goal_mode not in GOAL_MODES:
+        raise C.SrlzError("%s: goal_mode must be 'running' or 'final', got %r" % (who, goal_mode))
+    return goal, (s if goal.dim() == 2 else 0), GOAL_MODES[goal_mode]
+
+
+def rollout_goal(states, plans, wf, bf, goal, reward=None, final=None, returns=None, trajectory=None, reward_logits=None, goal_dist=None,
+                 gamma=1.0, goal_weight=1.0, goal_mode="running"):
+    """One launch of srlz_rollout_goal: rollout's arguments, goal fp32 [S] (shared by every environment, read with a stride of 0) or
+    [N,S], goal_weight > 0, goal_mode "running" / "final".  returns [N,K] is the score (allowed without a reward head), goal_dist
+    [N,K,T] the squared distance of every step; both written only when given.  Returns `final`."""
+    states = _rollout_f32(states, "states")
+    if states.dim() != 2:
+        raise C.SrlzError("rollout_goal: states [N,S] expected, got %s" % (tuple(states.shape),))
+    n, s = states.shape
+    wf = _rollout_f32(wf, "forward_net.weight")
+    if wf.dim() != 2 or wf.shape[0] != s or wf.shape[1] <= s:
+        raise C.SrlzError("rollout_goal: forward_net.weight of shape %s does not take states of %d dimensions" % (tuple(wf.shape), s))
+    a = wf.shape[1] - s
+    bf = _rollout_f32(bf, "forward_net.bias", (s,))
+    plans = rollout_plans(plans, a, states.device)
+    if plans.device != states.device or plans.dim() not in (2, 3) or (plans.dim() == 3 and plans.shape[0] != n):
+        raise C.SrlzError("rollout_goal: plans must be [N,K,T] with N = %d or [K,T] on the states' device, got %s" % (n, tuple(plans.shape)))
+    k, t = plans.shape[-2], plans.shape[-1]
+    stride = k * t if plans.dim() == 3 else 0
+    goal, gstride, mode = _goal_args(goal, n, s, goal_mode, "rollout_goal")
+    h, head = 0, (None,) * 6
+    if reward is not None:
+        h = reward[0].shape[0]
+        shapes = ((h, 2 * s), (h,), (h, h), (h,), (2, h), (2,))
+        head = tuple(_rollout_f32(p, "reward_net parameter", shape) for p, shape in zip(reward, shapes))
+    if final is None:
+        final = torch.empty((n, k, s), dtype=torch.float32, device=states.device)
+    final = _rollout_f32(final, "final", (n, k, s))
+    returns = _rollout_f32(returns, "returns", (n, k))
+    trajectory = _rollout_f32(trajectory, "trajectory", (n, k, t, s))
+    reward_logits = _rollout_f32(reward_logits, "reward_logits", (n, k, t, 2))
+    goal_dist = _rollout_f32(goal_dist, "goal_dist", (n, k, t))
+    C.rollout_goal(ptr(states), ptr(plans), stride, ptr(wf), ptr(bf), *[ptr(p) for p in head], ptr(final), ptr(returns), ptr(trajectory),
+                   ptr(reward_logits), n, k, t, s, a, h, 2, float(gamma), ptr(goal), gstride, float(goal_weight), mode, ptr(goal_dist),
+                   stream())
+    return final
+
+
+def plan_cem_goal(states, wf, bf, reward, goal, n_plans, horizon, iterations, elites, sharpness, best_plan, best_return, cum, workspace,
+                  gamma=1.0, seed=0, init_weights=None, plans=None, returns=None, goal_weight=1.0, goal_mode="running"):
+    """`iterations` launches of plan_cem_kernel<PlanGoalArgs>: plan_cem's arguments with the goal of rollout_goal; reward = (w1 .. b3) or None
+    (the score is then the goal term alone).  best_return and returns are scores."""
+    states = _rollout_f32(states, "states")
+    if states.dim() != 2:
+        raise C.SrlzError("plan_cem_goal: states [N,S] expected, got %s" % (tuple(states.shape),))
+    n, s = states.shape
+    wf = _rollout_f32(wf, "forward_net.weight")
+    if wf.dim() != 2 or wf.shape[0] != s or wf.shape[1] <= s:
+        raise C.SrlzError("plan_cem_goal: forward_net.weight of shape %s does not take states of %d dimensions" % (tuple(wf.shape), s))
+    a = wf.shape[1] - s
+    bf = _rollout_f32(bf, "forward_net.bias", (s,))
+    goal, gstride, mode = _goal_args(goal, n, s, goal_mode, "plan_cem_goal")
+    h, head = 0, (None,) * 6
+    if reward is not None:
+        h = reward[0].shape[0]
+        shapes = ((h, 2 * s), (h,), (h, h), (h,), (2, h), (2,))
+        head = tuple(_rollout_f32(p, "reward_net parameter", shape) for p, shape in zip(reward, shapes))
+    k, t, it = int(n_plans), int(horizon), int(iterations)
+    stride = 0
+    if init_weights is not None:
+        if tuple(init_weights.shape) not in ((t, a), (n, t, a)):
+            raise C.SrlzError("plan_cem_goal: init_weights must be [T,A] or [N,T,A], got %s" % (tuple(init_weights.shape),))
+        stride = t * a if init_weights.dim() == 3 else 0
+        init_weights = _plan_buf(init_weights, "init_weights", torch.int32, init_weights.shape)
+    best_plan = _plan_buf(best_plan, "best_plan", torch.int32, (n, t))
+    best_return = _plan_buf(best_return, "best_return", torch.float32, (n,))
+    cum = _plan_buf(cum, "cum", torch.int32, (n, t, a))
+    plans = _plan_buf(plans, "plans", torch.int32, (it, n, k, t))
+    returns = _plan_buf(returns, "returns", torch.float32, (it, n, k))
+    if not torch.is_tensor(workspace) or workspace.device.type != "cuda" or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise C.SrlzError("plan_cem_goal: workspace must be a contiguous uint8 device tensor")
+    C.plan_cem_goal(ptr(states), ptr(wf), ptr(bf), *[ptr(p) for p in head], ptr(init_weights), stride, ptr(best_plan), ptr(best_return),
+                    ptr(cum), ptr(plans), ptr(returns), ptr(workspace), workspace.numel(), n, k, t, s, a, h, 2, it, int(elites),
+                    int(sharpness), float(gamma), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(goal), gstride, float(goal_weight), mode, stream())
+    return best_plan
