@@ -1055,6 +1055,43 @@ int srlz_plan_cem_goal(const float* states, const float* wf, const float* bf, co
                        srlz_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The k-step error of the dynamics on a recorded sequence (csrc/horizon.hip; evaluation/predict_forward.py): the open-loop check of
+ * forwardModel (models/forward_inverse.py:21-31) and, on the imagined pairs, rewardModel (:78-95).  Two launches.
+ * srlz_horizon_rows.  A recorded sequence of N frames: states fp32 [N,S], actions int32 [N] (actions[i] leads from frame i to i + 1).
+ * M rows; row r starts at frame starts[r] and has len[r] steps (int32 [M] both).  The caller's contract, not checked on the device:
+ * 0 <= starts[r], 0 <= len[r] <= T and starts[r] + len[r] <= N - 1.  Row r is rolled as srlz_rollout rolls a row (the same text,
+ * csrc/rollout_tile.h) from s_0 = states[starts[r]] with a_t = actions[starts[r] + t] for t < len[r]; at step t < len[r], with
+ * x = states[starts[r] + t + 1], once s_{t+1} is in the tile:
+ *   err[r,t]  = sum_j fl(s_{t+1}[j] - x[j])^2                    the imagined state against the recorded one
+ *   base[r,t] = sum_j fl(states[starts[r]][j] - x[j])^2          "the state stays s_0" against the recorded one
+ * both in the order of the goal distance above (16 partials, partial q an fma chain over j = q, q + 16, .. ascending, then
+ * ((p_0 + p_1) + ..) + p_15), a function of S alone.  For t >= len[r], err and base are a quiet NaN and nothing of the sequence is
+ * read; a row that met an action outside [0, A) inside its steps has NaN err (not base) from that step on.
+ * Outputs err, base fp32 [M,T]; optional reward_logits [M,T,2] (needs the head) and trajectory [M,T,S], for t < len[r] the bits
+ * srlz_rollout leaves for the same actions; their entries at t >= len[r] hold the row rolled on with action 0 and mean nothing.
+ * The six reward pointers are all given or all NULL.  No atomics; a row's outputs do not depend on the other rows or on its place.
+ * Limits (srlz_horizon_supported; has_reward = 0: H and n_rewards are not looked at): those of srlz_rollout_supported — the two
+ * reductions' partials add 4.2 KB of LDS: 119 KB of 160 at S = 512, H = 32 — and 1 <= T <= 32, N >= 1, 1 <= M <= 2^31 - 33.
+ * srlz_horizon_sums.  Per horizon t: count[t] (int64) = rows with len[r] > t; sum_err[t], sum_base[t] (fp64) over exactly those rows
+ * (a NaN among them propagates); with reward_logits, labels (int32 [N], classes 0 / 1) and hits (int64 [T]) — all three or none —
+ * hits[t] = those rows whose class (reward_logits[r,t,1] > reward_logits[r,t,0] ? 1 : 0: torch's argmax, a tie or a NaN is class 0)
+ * equals labels[starts[r] + t], the reward stored at the transition's first frame.
+ * Order of each fp64 sum, a function of (M, T) alone: partial k of 512 adds the values of its rows r = k, k + 512, k + 1024, .. in
+ * ascending order from 0 (rows with len[r] <= t are skipped); then for h = 256, 128, .. 1: p[k] += p[k + h] for every k < h; the sum
+ * is p[0].  No atomics: two runs are bit-identical.
+ * Refused before any launch, nothing written: a partly given head (or half of logits / labels / hits), reward_logits without a
+ * head, a shape outside the limits: SRLZ_ERR_BAD_DESC; a missing required pointer SRLZ_ERR_NULL.
+ * ------------------------------------------------------------------------------------------------------------ */
+int srlz_horizon_supported(int S, int A, int H, int n_rewards, int has_reward);
+int srlz_horizon_rows(const float* states, const int* actions, const int* starts, const int* len, const float* wf, const float* bf,
+                      const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, float* err,
+                      float* base, float* reward_logits, float* trajectory, int N, int M, int T, int S, int A, int H, int n_rewards,
+                      srlz_stream_t stream);
+int srlz_horizon_sums(const float* err, const float* base, const float* reward_logits, const int* labels, const int* starts,
+                      const int* len, int M, int T, long long* count, double* sum_err, double* sum_base, long long* hits,
+                      srlz_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Debug / calibration hooks (not on the product path).
  * ------------------------------------------------------------------------------------------------------------ */
 /* Host-only: dump the virtual-grid program of a 64->64 convolution (tests interpret it on the CPU).

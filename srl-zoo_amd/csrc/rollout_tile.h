@@ -1,7 +1,8 @@
-// rollout_tile.h — the 32-row state tile of the deployment dynamics, shared by rollout.hip (plans the caller brings) and plan.hip (plans
-// sampled on the device): one text of the MFMA helper, the step loop and the reward head, instantiated once per source of rows.
+// rollout_tile.h — the 32-row state tile of the deployment dynamics, shared by rollout.hip (plans the caller brings), plan.hip (plans
+// sampled on the device) and horizon.hip (the recorded actions of a dataset, each step compared with the recorded state): one text of
+// the MFMA helper, the step loop and the reward head, instantiated once per source of rows.
 // A row source says which rows of the tile exist, which environment's state a row starts from, where its outputs go and which action
-// it takes at each step; everything else — every sum's order, every rounding — is the same text, so the two kernels leave the same
+// it takes at each step; everything else — every sum's order, every rounding — is the same text, so the kernels leave the same
 // bits for the same plans.  Internal to csrc/: included after common.h.
 #pragma once
 #include <math.h>
@@ -40,6 +41,17 @@ struct GoalArgs {
   float* dist;        // by output row, [T] each; may be NULL
 };
 
+// The third mode of the tile (ro_tile<Rows, RO_TRACK>, csrc/horizon.hip): no score; the reduction's target moves with the step — row
+// rows.target(i, t) of p.states itself, the recorded state that the imagined s_{t+1} is compared with — and next to that error the
+// distance the row's start state has to the same target.  A kernel argument of its own, as GoalArgs is.
+struct TrackArgs {
+  float *err, *base;  // by output row, [T] each: |s_{t+1} - target|^2 and |s_0 - target|^2; NaN where the row has no step t
+};
+
+// The tile's compile-time modes: the bare score, the goal term in the score (these two are the `Goal = false / true` the tile had,
+// and convert from it), the moving target.
+constexpr int RO_SCORE = 0, RO_GOAL = 1, RO_TRACK = 2;
+
 __host__ __device__ inline int ro_sp(int S) { return (S + RO_KC - 1) & ~(RO_KC - 1); }  // the tile's k, whole chunks
 
 // floats of LDS: state tile, 8 partial blocks, h1, h2, W2, W3, b1, b2, b3 (+2 pad), the goal distance's 16 partials a row, then
@@ -51,6 +63,11 @@ __host__ __device__ inline size_t ro_lds_bytes(int S, bool reward, bool goal = f
   return (fl + 2 * RO_ROWS) * 4;
 }
 
+// RO_TRACK: two reductions a step, the goal term's partials twice.
+__host__ __device__ inline size_t ro_track_lds_bytes(int S, bool reward) {
+  return ro_lds_bytes(S, reward, true) + (size_t)RO_GOAL_Q * RO_LD * 4;
+}
+
 inline int ro_supported(int S, int A, int H, int n_rewards) {
   return S >= 1 && S <= RO_MAX_S && A >= 1 && A <= RO_MAX_A && H >= 1 && H <= RO_MAX_H && n_rewards == 2;
 }
@@ -59,6 +76,11 @@ inline int ro_supported(int S, int A, int H, int n_rewards) {
 // head — and the tile with the goal's partials inside the CU's LDS.
 inline int ro_goal_supported(int S, int A, int H, int n_rewards, int has_reward) {
   return ro_supported(S, A, has_reward ? H : 1, has_reward ? n_rewards : 2) && ro_lds_bytes(S, has_reward != 0, true) <= RO_LDS_CAP;
+}
+
+// With the moving target (srlz_horizon_supported is this): the same limits, the tile with both reductions' partials inside the LDS.
+inline int ro_track_supported(int S, int A, int H, int n_rewards, int has_reward) {
+  return ro_supported(S, A, has_reward ? H : 1, has_reward ? n_rewards : 2) && ro_track_lds_bytes(S, has_reward != 0) <= RO_LDS_CAP;
 }
 
 // acc += st[32 x k-range] . W[j][koff + k]^T over the chunks c0, c0 + cstep, .. of 32 k each.  w (uniform) + woff (this lane's row
@@ -140,12 +162,16 @@ __device__ __forceinline__ float ro_goal_sum(const float* gq, int row) {
 //   void begin(int i)           called once by thread i < 32 of an existing row, before its first action is asked for
 //   int action(int i, int t)    row i's action at step t: asked once per step, in step order, by thread i < 32 alone and only
 //                               for an existing row — one step ahead of the step that uses it
-// Goal (compile time): the goal-distance term of include/srlz.h joins the score; gp is then given and `lds` is
-// ro_lds_bytes(S, reward, true) bytes.
-// Without it not one instruction of the goal term exists.
+// Mode (compile time).  RO_GOAL: the goal-distance term of include/srlz.h joins the score; gp is then given and `lds` is
+// ro_lds_bytes(S, reward, true) bytes.  RO_TRACK: tp is given, `lds` is ro_track_lds_bytes(S, reward) bytes, and the row source has
+//   long long target(int i, int t)   the row of p.states that row i's s_{t+1} is compared with, -1: the row has no step t (asked by
+//                                    any thread of an existing row)
+// Without a mode not one instruction of it exists.
 // Ends behind a workgroup barrier: every output of the tile has been issued by its thread.
-template <class Rows, bool Goal = false>
-__device__ __forceinline__ void ro_tile(const TileArgs& p, float* lds, Rows& rows, const GoalArgs* gp = nullptr) {
+template <class Rows, int Mode = RO_SCORE>
+__device__ __forceinline__ void ro_tile(const TileArgs& p, float* lds, Rows& rows, const GoalArgs* gp = nullptr,
+                                        const TrackArgs* tp = nullptr) {
+  constexpr bool Goal = Mode == RO_GOAL, Track = Mode == RO_TRACK;
   const int S = p.S, A = p.A, H = p.H, T = p.T;
   const bool reward = p.w1 != nullptr;
   const int sp = ro_sp(S), nblk = (S + 31) >> 5;
@@ -164,6 +190,8 @@ __device__ __forceinline__ void ro_tile(const TileArgs& p, float* lds, Rows& row
   }
   float* gq = nullptr;  // the goal distance's partials: gq[q * RO_LD + row]
   if constexpr (Goal) { gq = fp; fp += RO_GOAL_Q * RO_LD; }
+  [[maybe_unused]] float* bq = nullptr;  // (Track) the start state's distance to the same target, as gq
+  if constexpr (Track) { gq = fp; fp += RO_GOAL_Q * RO_LD; bq = fp; fp += RO_GOAL_Q * RO_LD; }
   int* act = (int*)fp;        // this step's action of each row, -1 = outside [0, A)
   int* bad = act + RO_ROWS;   // sticky: the row met an action outside [0, A)
 
@@ -270,6 +298,28 @@ __device__ __forceinline__ void ro_tile(const TileArgs& p, float* lds, Rows& row
       if (!reward) __syncthreads();  // (with a reward head its barriers stand between these writes and the row's sum)
     }
 
+    // ---- moving target: thread (row i, column group q), the goal distance's order twice — the tile and the row's start state
+    // against row target(i, t) of the states ----
+    if constexpr (Track) {
+      const int i = tid & 31, q = tid >> 5;
+      float part = 0.f, bpart = 0.f;
+      const long long tg = rows.exists(i) ? rows.target(i, t) : -1;
+      if (tg >= 0) {
+        const float* tl = p.states + tg * S;
+        const float* s0 = p.states + rows.env(i) * S;
+        for (int j = q; j < S; j += RO_GOAL_Q) {
+          const float x = tl[j];
+          const float e = __fsub_rn(st[j * RO_LD + i], x);
+          const float b = __fsub_rn(s0[j], x);
+          part = fmaf(e, e, part);
+          bpart = fmaf(b, b, bpart);
+        }
+      }
+      gq[q * RO_LD + i] = part;
+      bq[q * RO_LD + i] = bpart;
+      if (!reward) __syncthreads();  // (as above)
+    }
+
     // ---- s_{t+1} out: wave w writes rows 4w .. 4w+3 of the tile, a row's S floats along the lanes ----
     if (p.trajectory || (t == T - 1 && p.final_states)) {
       for (int i = wave * (RO_ROWS / RO_WAVES); i < (wave + 1) * (RO_ROWS / RO_WAVES); ++i) {
@@ -348,6 +398,15 @@ __device__ __forceinline__ void ro_tile(const TileArgs& p, float* lds, Rows& row
           const long long rg = rows.out(tid);
           if (gp->dist) gp->dist[rg * T + t] = d;
           if (t == T - 1 && p.returns) p.returns[rg] = ret;
+        }
+      }
+      if constexpr (Track) {
+        if (mine) {
+          const long long rg = rows.out(tid);
+          const bool has = rows.target(tid, t) >= 0;
+          const float e = ro_goal_sum(gq, tid), b = ro_goal_sum(bq, tid);
+          tp->err[rg * T + t] = has ? e : nanf_;
+          tp->base[rg * T + t] = has ? b : nanf_;
         }
       }
       if (t + 1 < T && mine) {  // the next step's action (read by the epilogue, two barriers from here)

@@ -286,6 +286,9 @@ _PROTOS = {
     "srlz_plan_goal_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
     "srlz_plan_cem_goal": (c_int, [P, P, P, P, P, P, P, P, P, P, c_longlong, P, P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int,
                                    c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_ulonglong, P, c_longlong, c_float, c_int, P]),
+    "srlz_horizon_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "srlz_horizon_rows": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "srlz_horizon_sums": (c_int, [P, P, P, P, P, P, c_int, c_int, P, P, P, P, P]),
 }
 
 # entry points whose int return value is data, not a status
@@ -299,7 +302,8 @@ _NOT_STATUS = {"srlz_version", "srlz_device_cus", "srlz_conv64_fwd_tiles", "srlz
                "srlz_dense_out_fwd_loss_workgroups", "srlz_reward_probe_chunk_rows", "srlz_infer_block_supported",
                "srlz_infer_tile", "srlz_conv64_bwd_fused_workgroups", "srlz_conv1_workgroups",
                "srlz_conv1_buffer_staging_supported", "srlz_infer_dec_supported", "srlz_infer_dec_tile", "srlz_rollout_supported",
-               "srlz_rollout_tile", "srlz_plan_supported", "srlz_rollout_goal_supported", "srlz_plan_goal_supported"}
+               "srlz_rollout_tile", "srlz_plan_supported", "srlz_rollout_goal_supported", "srlz_plan_goal_supported",
+               "srlz_horizon_supported"}
 
 EXPORTED = sorted(_PROTOS.keys())
 

@@ -609,6 +609,20 @@ def reconstruct(encoder, decoder, frames):
 # bits for the states and logits — where goal_route_for / plan_goal_route_for say so and within max_rows / max_horizon; otherwise
 # route "model": the model's own forwardModel / rewardModel step by step, scored by goal_scores (the rule written once, numpy or
 # torch), which also feeds cem_host.  A call without a goal takes exactly the path it always took.
+#
+# The dynamics' own metric.  Whether a trained forward head still means anything after `horizon` steps — the open-loop check on a
+# recorded sequence, which plan(horizon=...) rests on:
+#     h = dyn.horizon_error(states, actions, episode_starts, horizon=10, rewards=None, starts=None, keep_rows=False)
+#     h.count, h.mse, h.baseline_mse, h.ratio            # per horizon [T]; ratio below 1: the model beats "nothing moves"
+#     h.reward_accuracy, h.majority_accuracy             # with rewards and a trained reward head, else None
+#     h.err, h.base, h.logits                            # keep_rows: the rows [M,T], [M,T], [M,T,2]
+# From every start frame i the recorded actions a_i .. a_{i+L-1} go through the forward head, L = valid_steps: as far as the episode
+# and the horizon reach; the imagined state after t + 1 steps is compared with the recorded states[i + t + 1], next to the error of
+# "the state stays states[i]"; the reward head, on the imagined pairs, is asked for the reward stored at each transition's first
+# frame (-1 read as 0, the learner's own labelling).  mse = sum_err / (count * S), ratio = sum_err / sum_base.  Route "rollout" is
+# two launches of csrc/horizon.hip (include/srlz.h states every sum's order): the imagined states never leave the chip, and max_rows
+# does not apply — nothing is staged per row.  Route "model" is the model's own forwardModel / rewardModel step by step with fp64
+# sums on the host: SRLModulesSplit, head shapes srlz_horizon_supported refuses, horizons beyond 32 or max_horizon.
 # =============================================================================================================
 ROUTE_ROLLOUT = "rollout"
 HEADS = ("forward", "inverse", "reward")
@@ -851,6 +865,148 @@ def plan_goal_route_for(model, has_goal_only, n_plans, horizon, n_envs=1, max_ro
         return ROUTE_MODEL
     s, a, h, nr = dynamics_dims(model)
     return ROUTE_ROLLOUT if ops.plan_goal_supported(s, a, h, nr, not has_goal_only, n_plans, horizon) else ROUTE_MODEL
+
+
+# ---- the dynamics' own metric: the k-step error on a recorded sequence (include/srlz.h states the rule) ----
+HORIZON_MAX_T = 32  # steps one srlz_horizon_rows call takes
+
+
+class HorizonError(object):
+    """What LatentDynamics.horizon_error returns: numpy arrays per horizon [T]; a field the call has no head or no rewards for (or
+    did not ask for) is None."""
+    __slots__ = ("horizon", "count", "mse", "baseline_mse", "ratio", "reward_accuracy", "majority_accuracy", "err", "base", "logits",
+                 "sum_err", "sum_base", "hits")
+
+    def __init__(self, horizon, count, sum_err, sum_base, state_dim, hits=None, majority_accuracy=None, err=None, base=None, logits=None):
+        self.horizon, self.count = int(horizon), np.asarray(count, np.int64)
+        self.sum_err, self.sum_base = np.asarray(sum_err, np.float64), np.asarray(sum_base, np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            self.mse = self.sum_err / (self.count * float(state_dim))
+            self.baseline_mse = self.sum_base / (self.count * float(state_dim))
+            self.ratio = self.sum_err / self.sum_base
+            self.hits = None if hits is None else np.asarray(hits, np.int64)
+            self.reward_accuracy = None if hits is None else self.hits / self.count.astype(np.float64)
+        self.majority_accuracy = majority_accuracy
+        self.err, self.base, self.logits = err, base, logits
+
+    def as_dict(self):
+        """The JSON of evaluation.predict_forward: lists per horizon, None for what the call did not have; a value that is no
+        finite number (a horizon no row reaches) is None too."""
+        lst = lambda v: None if v is None else [float(x) if np.isfinite(x) else None for x in v]  # noqa: E731
+        return {"horizon": self.horizon, "count": [int(c) for c in self.count], "mse": lst(self.mse), "baseline_mse": lst(self.baseline_mse),
+                "ratio": lst(self.ratio), "reward_accuracy": lst(self.reward_accuracy), "majority_accuracy": lst(self.majority_accuracy)}
+
+
+def valid_steps(episode_starts, horizon):
+    """int32 [N]: for every frame i the largest L <= horizon such that frames i + 1 .. i + L exist and none of them starts an
+    episode — the steps of the recorded sequence an open-loop plan from frame i may take."""
+    es = np.asarray(episode_starts).reshape(-1) != 0
+    t = int(horizon)
+    if t < 1:
+        raise ValueError("horizon must be at least 1, got %r" % (horizon,))
+    n = es.shape[0]
+    first = np.flatnonzero(es)  # ascending
+    nxt = np.full(n, n, np.int64)  # the first episode start behind frame i, N when there is none
+    if first.size:
+        pos = np.searchsorted(first, np.arange(n), side="right")
+        nxt = np.where(pos < first.size, first[np.minimum(pos, first.size - 1)], n)
+    return np.minimum(nxt - 1 - np.arange(n), t).astype(np.int32)
+
+
+def reward_classes(rewards):
+    """Rewards as stored -> int64 classes, the learner's own labelling: negative rewards count as 0, then the integer cast; a class
+    outside [0, 2) raises ValueError."""
+    r = np.array(rewards, copy=True).reshape(-1)
+    r[r < 0] = 0
+    classes = r.astype(np.int64)
+    if classes.size and (classes.min() < 0 or classes.max() > 1):
+        raise ValueError("the reward head has two classes: after mapping -1 to 0 rewards must fall in [0, 2), found classes %s"
+                         % sorted(set(classes.tolist())))
+    return classes
+
+
+def horizon_totals(err, base, lens, logits=None, labels=None, starts=None):
+    """The per-horizon totals in numpy fp64 from rows err, base [M,T] (and logits [M,T,2] with labels [N], starts [M]):
+    (count, sum_err, sum_base, hits | None).  What route "model" sums with; srlz_horizon_sums' order differs, its rule is this one."""
+    err, base, lens = np.asarray(err, np.float64), np.asarray(base, np.float64), np.asarray(lens).reshape(-1)
+    t = err.shape[1]
+    valid = np.arange(t)[None, :] < lens[:, None]
+    count = valid.sum(axis=0).astype(np.int64)
+    sum_err = np.where(valid, err, 0.0).sum(axis=0)
+    sum_base = np.where(valid, base, 0.0).sum(axis=0)
+    hits = None
+    if logits is not None:
+        lg = np.asarray(logits)
+        with np.errstate(invalid="ignore"):
+            cls = (lg[..., 1] > lg[..., 0]).astype(np.int64)  # torch's argmax: a tie or a NaN is class 0
+        frame = np.minimum(np.asarray(starts, np.int64)[:, None] + np.arange(t)[None, :], len(labels) - 1)
+        hits = (valid & (cls == np.asarray(labels)[frame])).sum(axis=0).astype(np.int64)
+    return count, sum_err, sum_base, hits
+
+
+def majority_accuracy(labels, starts, lens, horizon):
+    """fp64 [T]: per horizon the share of the commoner class among labels[starts[r] + t] over the valid (r, t) — what a constant
+    answer scores.  From the labels alone."""
+    t = int(horizon)
+    starts, lens = np.asarray(starts, np.int64), np.asarray(lens).reshape(-1)
+    valid = np.arange(t)[None, :] < lens[:, None]
+    frame = np.minimum(starts[:, None] + np.arange(t)[None, :], len(labels) - 1)
+    ones = (valid & (np.asarray(labels)[frame] == 1)).sum(axis=0).astype(np.float64)
+    count = valid.sum(axis=0).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.maximum(ones, count - ones) / count
+
+
+def check_recording(states_n, actions, episode_starts, horizon, n_actions, starts=None):
+    """Validate the recorded sequence of a horizon_error call -> (actions int32 [N] on the host, starts int32 [M], lens int32 [M]).
+    ValueError: lengths that disagree, non-integer actions, a start outside the sequence, no start with a valid step, an action
+    outside [0, n_actions) inside a valid step."""
+    n = int(states_n)
+    if torch.is_tensor(actions):
+        actions = actions.detach().cpu().numpy()
+    actions = np.asarray(actions).reshape(-1)
+    if not np.issubdtype(actions.dtype, np.integer):
+        if not np.all(actions == np.floor(actions)):
+            raise ValueError("actions must be integers (got %s)" % (actions.dtype,))
+        actions = actions.astype(np.int64)
+    if torch.is_tensor(episode_starts):
+        episode_starts = episode_starts.detach().cpu().numpy()
+    es = np.asarray(episode_starts).reshape(-1)
+    if actions.shape[0] != n or es.shape[0] != n:
+        raise ValueError("states, actions and episode_starts must have one entry per frame, got %d, %d and %d" % (n, actions.shape[0], es.shape[0]))
+    lens_all = valid_steps(es, horizon)
+    if starts is None:
+        starts = np.flatnonzero(lens_all >= 1)
+    else:
+        if torch.is_tensor(starts):
+            starts = starts.detach().cpu().numpy()
+        starts = np.asarray(starts).reshape(-1)
+        if not np.issubdtype(starts.dtype, np.integer):
+            raise ValueError("starts must be integer frame indices (got %s)" % (starts.dtype,))
+        if starts.size and (starts.min() < 0 or starts.max() >= n):
+            raise ValueError("starts must lie in [0, %d), got %d .. %d" % (n, starts.min(), starts.max()))
+    if starts.size < 1:
+        raise ValueError("no start frame has a valid step: every frame is the last of its episode")
+    lens = lens_all[starts]
+    cover = np.zeros(n + 1, np.int64)  # frames whose action some row takes
+    np.add.at(cover, starts, 1)
+    np.add.at(cover, starts + lens, -1)
+    used = np.cumsum(cover)[:n] > 0
+    if used.any():
+        lo, hi = int(actions[used].min()), int(actions[used].max())
+        if lo < 0 or hi >= n_actions:
+            raise ValueError("actions must lie in [0, %d) inside every valid step, got %d .. %d" % (n_actions, lo, hi))
+    return np.where(used, actions, 0).astype(np.int32), starts.astype(np.int32), lens.astype(np.int32)
+
+
+def horizon_route_for(model, has_reward=True, horizon=1, max_horizon=32):
+    """The route LatentDynamics.horizon_error takes (host only: no GPU is asked for).  has_reward: the reward head is asked."""
+    from models.modules import SRLModules
+    owner = _dynamics_owner(model)
+    s, a, h, nr = dynamics_dims(model)
+    ok = isinstance(owner, SRLModules) and a >= 1 and owner.forward_net.bias is not None and \
+        1 <= int(horizon) <= min(HORIZON_MAX_T, int(max_horizon)) and ops.horizon_supported(s, a, h, nr, has_reward)
+    return ROUTE_ROLLOUT if ok else ROUTE_MODEL
 
 
 def philox4x32_10(counter, key):
@@ -1313,6 +1469,77 @@ class LatentDynamics(object):
             plans = plans[:, 0] if plans is not None else None
             returns = returns[:, 0] if returns is not None else None
         return Plan(best_plan, best_return, action, weights, plans, returns)
+
+    # ---- the k-step error on a recorded sequence ----
+    def _model_horizon(self, x, acts, starts, lens, t, reward):
+        """Route "model": the owner's own forwardModel / rewardModel step by step -> rows err, base fp32 [M,T] (NaN past a row's
+        steps) and logits [M,T,2] | None, on the device."""
+        n = x.shape[0]
+        nanv = torch.tensor(float("nan"), dtype=torch.float32, device=x.device)
+        errs, bases, logits = [], [], []
+        with torch.no_grad():
+            s0 = x[starts]
+            cur = s0
+            for step in range(t):
+                has = lens > step
+                frame = torch.clamp(starts + step, max=n - 1)
+                a = torch.where(has, acts[frame], torch.zeros_like(frame))
+                nxt = self.owner.forwardModel(cur, a.contiguous())
+                tgt = x[torch.clamp(starts + step + 1, max=n - 1)]
+                e = (nxt - tgt).double().pow(2).sum(dim=1).float()
+                b = (s0 - tgt).double().pow(2).sum(dim=1).float()
+                errs.append(torch.where(has, e, nanv))
+                bases.append(torch.where(has, b, nanv))
+                if reward:
+                    logits.append(self.owner.rewardModel(cur, nxt))
+                cur = nxt
+        return torch.stack(errs, dim=1), torch.stack(bases, dim=1), torch.stack(logits, dim=1) if reward else None
+
+    def horizon_error(self, states, actions, episode_starts, horizon, rewards=None, starts=None, keep_rows=False):
+        """The k-step error of the forward head on a recorded sequence -> HorizonError (the section comment above states the rule).
+        states [N,S] floating point (numpy or a device tensor), actions and episode_starts [N], rewards [N] as stored or None,
+        starts: frame indices [M] or None (every frame with a valid step)."""
+        self._need("forward")
+        n, single = check_states(states, self.state_dim)
+        if single:
+            raise ValueError("horizon_error takes a recorded sequence [N,S], got one bare state")
+        t = int(horizon)
+        acts, st, ln = check_recording(n, actions, episode_starts, t, self.n_actions, starts)
+        labels = None if rewards is None else reward_classes(rewards)
+        if labels is not None and labels.shape[0] != n:
+            raise ValueError("rewards must have one entry per frame, got %d for %d states" % (labels.shape[0], n))
+        reward = labels is not None and self._uses_reward()
+        kernel = not self._forced_model and horizon_route_for(self.owner, reward, t, self.max_horizon) == ROUTE_ROLLOUT
+        self.last_route = ROUTE_ROLLOUT if kernel else ROUTE_MODEL
+        dev = self.device
+        x = self._device_states(states, n, False, False)
+        d_acts = torch.from_numpy(acts).to(dev)
+        d_st, d_ln = torch.from_numpy(st).to(dev), torch.from_numpy(ln).to(dev)
+        m = st.shape[0]
+        if kernel:
+            o = self.owner
+            err = torch.empty((m, t), dtype=torch.float32, device=dev)
+            base = torch.empty((m, t), dtype=torch.float32, device=dev)
+            logits = torch.empty((m, t, 2), dtype=torch.float32, device=dev) if reward else None
+            rn = o.reward_net
+            head = (rn[0].weight, rn[0].bias, rn[2].weight, rn[2].bias, rn[4].weight, rn[4].bias) if reward else None
+            ops.horizon_rows(x, d_acts, d_st, d_ln, o.forward_net.weight, o.forward_net.bias, err, base, t, reward=head,
+                             reward_logits=logits)
+            count = torch.empty(t, dtype=torch.int64, device=dev)
+            sum_err = torch.empty(t, dtype=torch.float64, device=dev)
+            sum_base = torch.empty(t, dtype=torch.float64, device=dev)
+            hits = torch.empty(t, dtype=torch.int64, device=dev) if reward else None
+            d_lab = torch.from_numpy(labels.astype(np.int32)).to(dev) if reward else None
+            ops.horizon_sums(err, base, d_st, d_ln, count, sum_err, sum_base, reward_logits=logits, labels=d_lab, hits=hits)
+            count, sum_err, sum_base = count.cpu().numpy(), sum_err.cpu().numpy(), sum_base.cpu().numpy()
+            hits = hits.cpu().numpy() if reward else None
+        else:
+            err, base, logits = self._model_horizon(x, d_acts.long(), d_st.long(), d_ln.long(), t, reward)
+            count, sum_err, sum_base, hits = horizon_totals(err.cpu().numpy(), base.cpu().numpy(), ln,
+                                                            logits.cpu().numpy() if reward else None, labels, st)
+        major = majority_accuracy(labels, st, ln, t) if reward else None
+        rows = (err, base, logits) if keep_rows else (None, None, None)
+        return HorizonError(t, count, sum_err, sum_base, self.state_dim, hits, major, *rows)
 
     def _pair(self, states, next_states):
         n, single = check_states(states, self.state_dim)

@@ -2455,3 +2455,75 @@ def plan_cem_goal(states, wf, bf, reward, goal, n_plans, horizon, iterations, el
                     ptr(cum), ptr(plans), ptr(returns), ptr(workspace), workspace.numel(), n, k, t, s, a, h, 2, it, int(elites),
                     int(sharpness), float(gamma), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(goal), gstride, float(goal_weight), mode, stream())
     return best_plan
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# The k-step error of the dynamics on a recorded sequence (csrc/horizon.hip; include/srlz.h states the rule): two launches.  Thin,
+# as rollout: the caller (srlz/deploy.py) owns every buffer and checks the contract starts[r] + len[r] <= N - 1, 0 <= len[r] <= T.
+# ----------------------------------------------------------------------------------------------------------------
+def horizon_supported(s, a, h=16, n_rewards=2, has_reward=True):
+    return bool(C.horizon_supported(int(s), int(a), int(h), int(n_rewards), int(bool(has_reward))))
+
+
+def _horizon_t(t, name, dtype, shape):
+    if t is None:
+        return None
+    if not torch.is_tensor(t) or t.device.type != "cuda" or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise C.SrlzError("horizon: %s must be a contiguous %s device tensor of shape %s" % (name, dtype, tuple(shape)))
+    return t.detach()
+
+
+def horizon_rows(states, actions, starts, lens, wf, bf, err, base, horizon, reward=None, reward_logits=None, trajectory=None):
+    """One launch of srlz_horizon_rows.  states fp32 [N,S], actions int32 [N], starts / lens int32 [M]; err, base fp32 [M,T] with
+    T = horizon; reward = (w1, b1, w2, b2, w3, b3) or None; reward_logits [M,T,2] and trajectory [M,T,S] written only when given."""
+    states = _rollout_f32(states, "states")
+    if states.dim() != 2:
+        raise C.SrlzError("horizon: states [N,S] expected, got %s" % (tuple(states.shape),))
+    n, s = states.shape
+    wf = _rollout_f32(wf, "forward_net.weight")
+    if wf.dim() != 2 or wf.shape[0] != s or wf.shape[1] <= s:
+        raise C.SrlzError("horizon: forward_net.weight of shape %s does not take states of %d dimensions" % (tuple(wf.shape), s))
+    a = wf.shape[1] - s
+    bf = _rollout_f32(bf, "forward_net.bias", (s,))
+    t = int(horizon)
+    actions = _horizon_t(actions, "actions", torch.int32, (n,))
+    if starts is None or starts.dim() != 1:
+        raise C.SrlzError("horizon: starts [M] expected")
+    m = starts.shape[0]
+    starts = _horizon_t(starts, "starts", torch.int32, (m,))
+    lens = _horizon_t(lens, "lens", torch.int32, (m,))
+    h, head = 0, (None,) * 6
+    if reward is not None:
+        h = reward[0].shape[0]
+        shapes = ((h, 2 * s), (h,), (h, h), (h,), (2, h), (2,))
+        head = tuple(_rollout_f32(p, "reward_net parameter", shape) for p, shape in zip(reward, shapes))
+    err = _rollout_f32(err, "err", (m, t))
+    base = _rollout_f32(base, "base", (m, t))
+    reward_logits = _rollout_f32(reward_logits, "reward_logits", (m, t, 2))
+    trajectory = _rollout_f32(trajectory, "trajectory", (m, t, s))
+    C.horizon_rows(ptr(states), ptr(actions), ptr(starts), ptr(lens), ptr(wf), ptr(bf), *[ptr(p) for p in head], ptr(err), ptr(base),
+                   ptr(reward_logits), ptr(trajectory), n, m, t, s, a, h, 2, stream())
+    return err, base
+
+
+def horizon_sums(err, base, starts, lens, count, sum_err, sum_base, reward_logits=None, labels=None, hits=None):
+    """One launch of srlz_horizon_sums: err, base fp32 [M,T] -> count int64 [T], sum_err / sum_base fp64 [T]; with reward_logits
+    [M,T,2], labels int32 [N] and hits int64 [T] (all three or none) the per-horizon hit counts of the reward head."""
+    err = _rollout_f32(err, "err")
+    if err.dim() != 2:
+        raise C.SrlzError("horizon: err [M,T] expected, got %s" % (tuple(err.shape),))
+    m, t = err.shape
+    base = _rollout_f32(base, "base", (m, t))
+    starts = _horizon_t(starts, "starts", torch.int32, (m,))
+    lens = _horizon_t(lens, "lens", torch.int32, (m,))
+    count = _horizon_t(count, "count", torch.int64, (t,))
+    sum_err = _horizon_t(sum_err, "sum_err", torch.float64, (t,))
+    sum_base = _horizon_t(sum_base, "sum_base", torch.float64, (t,))
+    reward_logits = _rollout_f32(reward_logits, "reward_logits", (m, t, 2))
+    if labels is not None and (not torch.is_tensor(labels) or labels.device.type != "cuda" or labels.dtype != torch.int32
+                               or labels.dim() != 1 or not labels.is_contiguous()):
+        raise C.SrlzError("horizon: labels must be a contiguous int32 device tensor [N]")
+    hits = _horizon_t(hits, "hits", torch.int64, (t,))
+    C.horizon_sums(ptr(err), ptr(base), ptr(reward_logits), ptr(labels), ptr(starts), ptr(lens), m, t, ptr(count), ptr(sum_err),
+                   ptr(sum_base), ptr(hits), stream())
+    return count, sum_err, sum_base, hits
