@@ -85,3 +85,69 @@ def test_dense_launcher_shape_predicate(cabi):
     assert cabi.dense_in_workspace(512, 50, 3 * P) > 0
     assert cabi.dense_out_bwd_workspace(512, 50, 3 * P) >= 512 * 3 * P * 4
     assert cabi.dense_out_fwd_loss_workgroups(512, 3 * P) == 8 * (3 * P // 64)
+
+
+# (M, n, plane, C, Z): the smallest shapes at which each edge of the tile kernel exists (K = C * plane), with the number Z of split-K
+# partials that in_split() of csrc/dense.hip takes there.  test_dense_entry_gpu.py runs the kernels at exactly these.
+#   1 x 1, K 3          everything at its minimum
+#   7 x 50, K 105       channel boundaries at k = 35, 70 inside the first tile and r-steps; last chunk 9 long
+#   33 x 63, K 126      six planes (the channel wraps 0,1,2,0,1,2); the ones column is lane 63 of tile 0; M = one r-step + 1
+#   64 x 64, K 384      every edge exact; the ones column opens a tile of its own
+#   65 x 65, K 8223     four output tiles, two r-steps per chunk (rchunk 64), last chunk 31 long; a row and a column behind a full tile
+#   130 x 256, K 33     n at its limit; K = one r-step + 1; three i-tiles, the last of 2 rows; the ones column alone in a fifth tile
+#   96 x 200, K 600     M = exactly three r-steps as the reduction
+DENSE_EDGE_SHAPES = [(1, 1, 1, 3, 1), (7, 50, 35, 3, 4), (33, 63, 21, 6, 4), (64, 64, 64, 6, 12), (65, 65, 2741, 3, 129),
+                     (130, 256, 11, 3, 2), (96, 200, 100, 6, 19)]
+
+
+def replay_in_split(M, n, K):
+    """in_split() / rchunk_for() of csrc/dense.hip: (Z, rchunk)."""
+    cdiv = lambda a, b: (a + b - 1) // b  # noqa: E731
+    tiles = cdiv(M, 64) * cdiv(n, 64)
+    want = 1 if tiles >= 1024 else cdiv(1024, tiles)
+    steps = cdiv(K, 32)
+    rchunk = cdiv(steps, min(want, steps)) * 32
+    return cdiv(K, rchunk), rchunk
+
+
+def assert_dense_split_table(cabi, M, n, plane, C, Z):
+    """The queries of the library against the table (and against the replay): a case written for Z partials cannot test another split."""
+    K = C * plane
+    assert cabi.dense_supported(M, n, K, plane) == 1
+    assert replay_in_split(M, n, K)[0] == Z
+    assert cabi.dense_in_workspace(M, n, K) == Z * M * n * 4
+    assert cabi.dense_out_bwd_workspace(M, n, K) == Z * M * n * 4 + M * K * 4
+    assert cabi.dense_out_fwd_loss_workgroups(M, K) == ((M + 63) // 64) * ((K + 63) // 64)
+
+
+@pytest.mark.parametrize("M,n,plane,C,Z", DENSE_EDGE_SHAPES)
+def test_dense_split_of_the_edge_shapes(cabi, M, n, plane, C, Z):
+    assert_dense_split_table(cabi, M, n, plane, C, Z)
+
+
+def test_dense_edge_shapes_reach_what_they_are_listed_for():
+    rc = {s[:2]: replay_in_split(s[0], s[1], s[2] * s[3])[1] for s in DENSE_EDGE_SHAPES}
+    assert rc[(65, 65)] == 64 and 8223 % 64 == 31            # two r-steps per chunk, a short last chunk
+    assert rc[(7, 50)] == 32 and 105 % 32 == 9
+    assert all(v == 32 for k, v in rc.items() if k != (65, 65))
+    assert replay_in_split(512, 50, 3 * 224 * 224) == (128, 1184)  # the workload's split, for comparison
+
+
+def test_dense_supported_at_the_32_bit_edges(cabi):
+    """Every offset of the kernels is a 32-bit int: M * K, (n + 1) * K (W with the ones column) and Z * M * n must stay below 2^31."""
+    ok = cabi.dense_supported
+    # M * K: K = 3 (one pixel per plane), Z = 1, n = 1
+    assert 715827882 * 3 < 2 ** 31 <= 715827883 * 3
+    assert ok(715827882, 1, 3, 1) == 1
+    assert ok(715827883, 1, 3, 1) == 0 and "32-bit" in cabi.error_text()
+    # (n + 1) * K at n = 256
+    assert 257 * 8355966 < 2 ** 31 <= 257 * 8355969
+    assert ok(1, 256, 8355966, 2785322) == 1
+    assert ok(1, 256, 8355969, 2785323) == 0 and "32-bit" in cabi.error_text()
+    # Z * M * n: Z = 1 at K = 3, M * n = 2^31 - 4 and 2^31 while M * K stays below
+    assert replay_in_split(536870911, 4, 3)[0] == 1 and 536870912 * 3 < 2 ** 31
+    assert ok(536870911, 4, 3, 1) == 1
+    assert ok(536870912, 4, 3, 1) == 0 and "split-K" in cabi.error_text()
+    # the workspace queries answer 0 to a shape that is none
+    assert cabi.dense_in_workspace(0, 4, 3) == 0 and cabi.dense_out_bwd_workspace(4, 0, 3) == 0
+    assert cabi.dense_out_fwd_loss_workgroups(0, 3) == -1 and cabi.dense_out_fwd_loss_workgroups(4, 0) == -1
