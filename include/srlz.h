@@ -1055,6 +1055,51 @@ int srlz_plan_cem_goal(const float* states, const float* wf, const float* bf, co
                        srlz_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Deployment tree search (csrc/beam.hip): exact enumeration or a beam of width W over the discrete action sequences of the dynamics
+ * above, ONE launch per level of the tree, enqueued back to back on the caller's stream with no host synchronisation between them;
+ * no plan and no frontier ever exists on the host.  Composed on the same reference lines as srlz_rollout — forwardModel
+ * (models/forward_inverse.py:21-31) for every expanded node's state, rewardModel (:78-95) for prob_t when a reward head is given.
+ * N environments, horizon T, beam width W >= 1, A actions, gamma; optionally the goal of srlz_rollout_goal (goal == NULL: no goal).
+ * Without a goal the reward head is required; with one it is optional.  Per environment, for levels t = 0 .. T-1:
+ *   frontier  level t has F_t nodes; F_0 = 1: the environment's state, ret = 0, g_0 = 1.
+ *   expand    every node f by every action a: child c = f * A + a, C_t = F_t * A children.  A child's state is one forward step of
+ *             its parent's state with the bits of srlz_rollout's step; its ret continues its parent's ret with this step's term under
+ *             the arithmetic of srlz_rollout (no goal: ret = ret + g_t * prob_t as srlz_rollout evaluates it) or srlz_rollout_goal
+ *             (fl(w * c_t), fl(prob_t - .), fl(g_t * term_t), fl(ret + .), each rounded on its own; in mode final c_t = d_t at level
+ *             T-1 alone, 0 before); g_{t+1} = fl(g_t * gamma).  The ret of every leaf is, bit for bit, what srlz_rollout (or
+ *             srlz_rollout_goal with the same goal, weight and mode) returns for that leaf's T-step plan.
+ *   select    (t < T-1)  C_t <= W: the next frontier is all children in child-index order, F_{t+1} = C_t.  Otherwise key = ret, NaN
+ *             read as -inf (and -0 as +0); order by key descending, then c ascending; the first W children in that order are the
+ *             next frontier, in that order, F_{t+1} = W.
+ *   leaves    (t = T-1)  all L = F_{T-1} * A children, in child-index order.  best = the leaf with the greatest key, ties to the
+ *             lowest c; best_return = its true ret (NaN included); best_plan = its actions, read back through the parents.
+ * With W >= A^(T-1) nothing is ever pruned: the leaves are all A^T plans in lexicographic order (a_0 the most significant digit) and
+ * best is the optimum under the model — the argmax srlz_rollout over the enumeration gives, at A + A^2 + .. + A^T forward steps in
+ * place of T * A^T.
+ * Outputs: best_plan int32 [N,T], best_return [N]; optional leaf_plans int32 [N,L,T] with leaf_returns [N,L] (both or neither),
+ * L = srlz_beam_leaves(W, A, T) (0 outside the limits).
+ * Workspace: srlz_beam_workspace(N, W, T, S, A) bytes (0 for a refused shape), 16-byte aligned: the environments' tickets (N uint32,
+ * zeroed on the stream when the call starts and zero again when its last launch has ended), two return buffers [N,L], the
+ * frontiers [T-1,N,W] and two child-state buffers [N,C_{T-2},S] used in turn — a selected child's state is read in place by the
+ * next level, nothing is copied; the last level writes no states.
+ * Per level N * ceil(C_t / 32) workgroups: a tile of 32 children never straddles two environments.  On a level that prunes, and on
+ * the last, the workgroup that finishes an environment last (the integer ticket of srlz_plan_cem, no spinning, no grid barrier) sorts
+ * 64-bit (key, c) words in LDS with integer compares alone, or takes their minimum.  No float atomics: two runs are bit-identical.
+ * Limits (srlz_beam_supported; has_reward = 0: H and n_rewards are not looked at): those of srlz_rollout_supported /
+ * srlz_rollout_goal_supported, and 1 <= T <= 32, W >= 1, W * A <= 8192.  Outside them, N < 1 or N * L above 2^31 - 33, a partly given
+ * head, no head and no goal, half the leaves, or a goal argument srlz_rollout_goal would refuse: SRLZ_ERR_BAD_DESC before anything is
+ * enqueued, nothing written; a missing required pointer SRLZ_ERR_NULL, a short workspace SRLZ_ERR_WORKSPACE.
+ * ------------------------------------------------------------------------------------------------------------ */
+int srlz_beam_supported(int S, int A, int H, int n_rewards, int has_reward, int W, int T);
+size_t srlz_beam_workspace(int N, int W, int T, int S, int A);
+int srlz_beam_leaves(int W, int A, int T);
+int srlz_beam_search(const float* states, const float* wf, const float* bf, const float* w1, const float* b1, const float* w2,
+                     const float* b2, const float* w3, const float* b3, int* best_plan, float* best_return, int* leaf_plans,
+                     float* leaf_returns, void* ws, size_t ws_bytes, int N, int W, int T, int S, int A, int H, int n_rewards,
+                     float gamma, const float* goal, long long goal_env_stride, float goal_weight, int goal_mode,
+                     srlz_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * The k-step error of the dynamics on a recorded sequence (csrc/horizon.hip; evaluation/predict_forward.py): the open-loop check of
  * forwardModel (models/forward_inverse.py:21-31) and, on the imagined pairs, rewardModel (:78-95).  Two launches.
  * srlz_horizon_rows.  A recorded sequence of N frames: states fp32 [N,S], actions int32 [N] (actions[i] leads from frame i to i + 1).

@@ -286,6 +286,11 @@ _PROTOS = {
     "srlz_plan_goal_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
     "srlz_plan_cem_goal": (c_int, [P, P, P, P, P, P, P, P, P, P, c_longlong, P, P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int,
                                    c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_ulonglong, P, c_longlong, c_float, c_int, P]),
+    "srlz_beam_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "srlz_beam_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "srlz_beam_leaves": (c_int, [c_int, c_int, c_int]),
+    "srlz_beam_search": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                 c_float, P, c_longlong, c_float, c_int, P]),
     "srlz_horizon_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "srlz_horizon_rows": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "srlz_horizon_sums": (c_int, [P, P, P, P, P, P, c_int, c_int, P, P, P, P, P]),
@@ -303,7 +308,7 @@ _NOT_STATUS = {"srlz_version", "srlz_device_cus", "srlz_conv64_fwd_tiles", "srlz
                "srlz_infer_tile", "srlz_conv64_bwd_fused_workgroups", "srlz_conv1_workgroups",
                "srlz_conv1_buffer_staging_supported", "srlz_infer_dec_supported", "srlz_infer_dec_tile", "srlz_rollout_supported",
                "srlz_rollout_tile", "srlz_plan_supported", "srlz_rollout_goal_supported", "srlz_plan_goal_supported",
-               "srlz_horizon_supported"}
+               "srlz_horizon_supported", "srlz_beam_supported", "srlz_beam_leaves"}
 
 EXPORTED = sorted(_PROTOS.keys())
 

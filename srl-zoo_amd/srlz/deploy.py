@@ -610,6 +610,24 @@ def reconstruct(encoder, decoder, frames):
 # route "model": the model's own forwardModel / rewardModel step by step, scored by goal_scores (the rule written once, numpy or
 # torch), which also feeds cem_host.  A call without a goal takes exactly the path it always took.
 #
+# Tree search.  The actions of this zoo are discrete and few; where the tree fits, search it instead of sampling it:
+#     r = dyn.search(states, horizon, beam=64, gamma=1.0, keep_leaves=False, goal=None, goal_weight=1.0, goal_mode="running")
+#     r.best_plan, r.best_return, r.action      # int32 [N,T], fp32 [N], int64 [N] (= best_plan[:, 0]); no host synchronisation
+#     r.exact, r.expanded, r.leaves             # nothing was pruned; forward steps per environment (sum of C_t); L
+#     r.leaf_plans, r.leaf_returns              # keep_leaves: int32 [N,L,T], fp32 [N,L]; else None
+#     p = reach(encoder, dyn, frames, goal_frames, horizon, planner="search", beam=64)
+# Level by level (include/srlz.h states it exactly): every node of the frontier is expanded by every action, child c = f * A + a;
+# while the children are at most `beam` all of them go on, otherwise the `beam` best by (ret descending — NaN as -inf — then c
+# ascending); the leaves are the last level's children, best the greatest among them, ties to the lowest c.  A prefix is expanded
+# once: A + A^2 + .. + A^T forward steps for all A^T leaves where rollout over the enumerated plans runs T * A^T.  With
+# beam >= A^(T-1) nothing is pruned (exact): the leaves are all A^T plans in lexicographic order and best_plan is the optimum under
+# the model — what plan() approaches by sampling.  Route "rollout" is `horizon` launches of csrc/beam.hip back to back on the current
+# stream; every leaf's return has the bits dyn.rollout gives for that leaf's plan (with the same goal, weight and mode).  Where
+# search_route_for says so — SRLModulesSplit, shapes srlz_beam_supported refuses (beam * A beyond 8192, more than 32 steps) and calls
+# of more than max_rows children a level — route "model" runs the same algorithm in numpy (beam_host) over this object's own returns
+# of the prefix plans (_run / _run_goal).  Heads and goals are gated as in plan; buffers are made on the first search call and grown
+# on demand; what a call returns are views of them, valid until the next call.
+#
 # The dynamics' own metric.  Whether a trained forward head still means anything after `horizon` steps — the open-loop check on a
 # recorded sequence, which plan(horizon=...) rests on:
 #     h = dyn.horizon_error(states, actions, episode_starts, horizon=10, rewards=None, starts=None, keep_rows=False)
@@ -867,6 +885,89 @@ def plan_goal_route_for(model, has_goal_only, n_plans, horizon, n_envs=1, max_ro
     return ROUTE_ROLLOUT if ops.plan_goal_supported(s, a, h, nr, not has_goal_only, n_plans, horizon) else ROUTE_MODEL
 
 
+# ---- the tree search's host side: sizes, argument checks, the route table and the same algorithm in numpy (route "model") ----
+class Search(object):
+    """What LatentDynamics.search returns.  best_plan int32 [N,T], best_return fp32 [N], action int64 [N] (= best_plan[:, 0]);
+    exact: nothing was pruned (best_plan is the optimum under the model), expanded: forward steps per environment (the sum of C_t),
+    leaves: L; leaf_plans int32 [N,L,T] and leaf_returns fp32 [N,L] (keep_leaves) or None; a bare state drops the N axis everywhere.
+    All tensors on the device."""
+    __slots__ = ("best_plan", "best_return", "action", "exact", "expanded", "leaves", "leaf_plans", "leaf_returns")
+
+    def __init__(self, best_plan, best_return, action, exact, expanded, leaves, leaf_plans=None, leaf_returns=None):
+        self.best_plan, self.best_return, self.action, self.exact, self.expanded, self.leaves, self.leaf_plans, self.leaf_returns = \
+            best_plan, best_return, action, exact, expanded, leaves, leaf_plans, leaf_returns
+
+
+def check_search_args(horizon, beam):
+    """Validate a search call's numbers (host only).  Returns them as ints: (horizon, beam)."""
+    vals = []
+    for name, v in (("horizon", horizon), ("beam", beam)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+        vals.append(int(v))
+    if vals[0] < 1 or vals[1] < 1:
+        raise ValueError("horizon and beam must be at least 1, got %d and %d" % tuple(vals))
+    return tuple(vals)
+
+
+def search_sizes(beam, horizon, n_actions):
+    """The tree of a search call, per environment (host only): dict of frontier [T] = F_t, children [T] = C_t = F_t * A (F_0 = 1,
+    F_{t+1} = min(C_t, beam)), leaves = L = C_{T-1}, exact (no level before the last has more than `beam` children: beam >= A^(T-1)),
+    expanded (forward steps: the sum of C_t)."""
+    t, w = check_search_args(horizon, beam)
+    a = int(n_actions)
+    if a < 1:
+        raise ValueError("n_actions must be at least 1, got %d" % a)
+    frontier, children, f = [], [], 1
+    for _ in range(t):
+        frontier.append(f)
+        children.append(f * a)
+        f = min(f * a, w)
+    return dict(frontier=frontier, children=children, leaves=children[-1], exact=all(c <= w for c in children[:-1]),
+                expanded=sum(children))
+
+
+def search_route_for(model, beam, horizon, n_envs=1, max_rows=8192, has_goal_only=False):
+    """The route LatentDynamics.search takes for a call of n_envs states (host only: no GPU is asked for).  has_goal_only: the
+    reward head stays out of the score, as in goal_route_for.  A beam wider than the tree's widest frontier counts as that frontier."""
+    if goal_route_for(model, has_goal_only) != ROUTE_ROLLOUT:
+        return ROUTE_MODEL
+    s, a, h, nr = dynamics_dims(model)
+    t, w = check_search_args(horizon, beam)
+    if t > 64:  # (far beyond the kernel's 32 steps; the tree's sizes are not needed to say so)
+        return ROUTE_MODEL
+    sizes = search_sizes(w, t, a)
+    w = max(sizes["frontier"])
+    if w * a > 2 ** 20 or n_envs * sizes["leaves"] > max_rows:
+        return ROUTE_MODEL
+    return ROUTE_ROLLOUT if ops.beam_supported(s, a, h, nr, not has_goal_only, w, t) else ROUTE_MODEL
+
+
+def beam_host(score_fn, n, beam, horizon, n_actions):
+    """The tree search on the host, the algorithm of csrc/beam.hip in numpy over score_fn(plans int32 [N,C,t+1]) -> fp32 [N,C]: the
+    ret of each prefix plan (what a (t+1)-step rollout returns for it; at t + 1 = horizon the leaf's return).
+    Returns a dict: best_plan int32 [N,T], best_return fp32 [N], leaf_plans int32 [N,L,T], leaf_returns fp32 [N,L], exact, expanded."""
+    sizes = search_sizes(beam, horizon, n_actions)
+    a = int(n_actions)
+    prefixes = np.zeros((n, 1, 0), np.int32)
+    for t in range(horizon):
+        f = prefixes.shape[1]
+        last = np.broadcast_to(np.tile(np.arange(a, dtype=np.int32), f)[None, :, None], (n, f * a, 1))
+        children = np.concatenate((np.repeat(prefixes, a, axis=1), last), axis=2)  # child c = f * A + a
+        ret = np.asarray(score_fn(children), np.float32).reshape(n, f * a)
+        key = np.where(np.isnan(ret), np.float32(-np.inf), ret)
+        if t == horizon - 1:
+            break
+        if f * a > beam:
+            order = np.argsort(-key, axis=1, kind="stable")[:, :beam]  # key descending, ties in c ascending
+            children = np.take_along_axis(children, order[:, :, None], axis=1)
+        prefixes = children
+    top = np.argmax(key, axis=1)  # the first maximum: ties go to the lowest c
+    rows = np.arange(n)
+    return dict(best_plan=children[rows, top].copy(), best_return=ret[rows, top].copy(), leaf_plans=children, leaf_returns=ret,
+                exact=sizes["exact"], expanded=sizes["expanded"])
+
+
 # ---- the dynamics' own metric: the k-step error on a recorded sequence (include/srlz.h states the rule) ----
 HORIZON_MAX_T = 32  # steps one srlz_horizon_rows call takes
 
@@ -1102,6 +1203,7 @@ class LatentDynamics(object):
         self._route, self.last_route = picked, None
         self._plan_bufs = {}  # the planner's device buffers: made by the first plan call
         self._goal_bufs = {}  # the goal calls' device buffers: made by the first call with a goal
+        self._search_bufs = {}  # the tree search's device buffers: made by the first search call
         self._forced_model = route is not None
         self.device = next(self.owner.forward_net.parameters()).device
         if self.device.type != "cuda":
@@ -1470,6 +1572,81 @@ class LatentDynamics(object):
             returns = returns[:, 0] if returns is not None else None
         return Plan(best_plan, best_return, action, weights, plans, returns)
 
+    # ---- tree search ----
+    def _search_buffers(self, n, w, t, leaves, keep):
+        """The search's device buffers, made on the first search call and grown only when a call asks for more."""
+        want = dict(best=n * t, ret=n, act=n, ws=ops.beam_workspace(n, w, t, self.state_dim, self.n_actions),
+                    lp=n * leaves * t if keep else 0, lr=n * leaves if keep else 0)
+        kinds = dict(best=torch.int32, ret=torch.float32, act=torch.int64, ws=torch.uint8, lp=torch.int32, lr=torch.float32)
+        have = self._search_bufs
+        for name, numel in want.items():
+            if name not in have or have[name].numel() < numel:
+                have[name] = torch.empty(max(numel, 1), dtype=kinds[name], device=self.device)
+        return have
+
+    def search(self, states, horizon, beam=64, gamma=1.0, keep_leaves=False, goal=None, goal_weight=1.0, goal_mode="running"):
+        """Exact or beam tree search for each environment's action sequence (the comment block above states it) -> Search.
+        With a goal the nodes are keyed by the score (best_return and leaf_returns are scores) and only the forward head is required."""
+        self._need("forward")
+        if goal is None:
+            self._need("reward")
+        n, single = check_states(states, self.state_dim)
+        t, w = check_search_args(horizon, beam)
+        a = self.n_actions
+        reward = True
+        if goal is not None:
+            goal_shared = check_goal(goal, n, self.state_dim)
+            gw, gmode = check_goal_args(goal_weight, goal_mode)
+            reward = self._goal_reward()
+        kernel = not self._forced_model and (goal is not None or self._route == ROUTE_ROLLOUT) and \
+            search_route_for(self.owner, w, t, n, self.max_rows, has_goal_only=not reward) == ROUTE_ROLLOUT
+        sizes = search_sizes(w, t, a)
+        leaves = sizes["leaves"]
+        if not kernel:
+            def score_fn(pl):
+                shape, arg = (n, pl.shape[1]), (pl[0] if single else pl)
+                if goal is None:
+                    r = self._run(states, arg, float(gamma), True, False, False)[1]
+                elif gmode == "running" or pl.shape[2] == t:
+                    r = self._run_goal(states, arg, goal, float(gamma), gw, gmode, reward, False, False, False)[1]
+                elif reward:  # (goal mode final: the distance enters at the last level alone)
+                    r = self._run(states, arg, float(gamma), True, False, False)[1]
+                else:
+                    return np.zeros(shape, np.float32)
+                return r.reshape(shape).float().cpu().numpy()
+            out = beam_host(score_fn, n, w, t, a)
+            self.last_route = ROUTE_MODEL
+            dev = self.device
+            best_plan = torch.from_numpy(out["best_plan"]).to(dev)
+            best_return = torch.from_numpy(out["best_return"]).to(dev)
+            action = best_plan[:, 0].to(torch.int64)
+            leaf_plans = torch.from_numpy(np.ascontiguousarray(out["leaf_plans"])).to(dev) if keep_leaves else None
+            leaf_returns = torch.from_numpy(np.ascontiguousarray(out["leaf_returns"])).to(dev) if keep_leaves else None
+        else:
+            self.last_route = ROUTE_ROLLOUT
+            w = max(sizes["frontier"])  # (a wider beam never prunes more: the same search)
+            gl = None
+            if goal is not None:
+                self._goal_buffers(n)
+                gl = self._device_goal(goal, goal_shared, n, True)
+            x = self._device_states(states, n, single, True)
+            b = self._search_buffers(n, w, t, leaves, keep_leaves)
+            best_plan, best_return = b["best"][:n * t].view(n, t), b["ret"][:n]
+            leaf_plans = b["lp"][:n * leaves * t].view(n, leaves, t) if keep_leaves else None
+            leaf_returns = b["lr"][:n * leaves].view(n, leaves) if keep_leaves else None
+            o, rn = self.owner, self.owner.reward_net
+            head = (rn[0].weight, rn[0].bias, rn[2].weight, rn[2].bias, rn[4].weight, rn[4].bias) if reward else None
+            ops.beam_search(x, o.forward_net.weight, o.forward_net.bias, head, w, t, best_plan, best_return, b["ws"], gamma=gamma,
+                            leaf_plans=leaf_plans, leaf_returns=leaf_returns, goal=gl, goal_weight=gw if goal is not None else 1.0,
+                            goal_mode=gmode if goal is not None else "running")
+            action = b["act"][:n]
+            action.copy_(best_plan[:, 0])
+        if single:
+            best_plan, best_return, action = best_plan[0], best_return[0], action[0]
+            leaf_plans = leaf_plans[0] if leaf_plans is not None else None
+            leaf_returns = leaf_returns[0] if leaf_returns is not None else None
+        return Search(best_plan, best_return, action, sizes["exact"], sizes["expanded"], leaves, leaf_plans, leaf_returns)
+
     # ---- the k-step error on a recorded sequence ----
     def _model_horizon(self, x, acts, starts, lens, t, reward):
         """Route "model": the owner's own forwardModel / rewardModel step by step -> rows err, base fp32 [M,T] (NaN past a row's
@@ -1579,15 +1756,17 @@ def imagine(dynamics, decoder, states, plans):
     return frames.view(tuple(traj.shape[:-1]) + tuple(frames.shape[1:]))
 
 
-def reach(encoder, dynamics, frames, goal_frames, horizon, **plan_kwargs):
+def reach(encoder, dynamics, frames, goal_frames, horizon, planner="cem", **plan_kwargs):
     """Plan from camera frames towards goal pictures: dynamics.plan(encoder(frames), horizon, goal=encoder(goal_frames), ...) -> Plan,
-    the states never leaving the device.  frames and goal_frames of the same shape ([N, ...] or one bare frame each); when both fit
+    or with planner="search" dynamics.search(...) with the same goal -> Search; the states never leaving the device.  frames and goal_frames of the same shape ([N, ...] or one bare frame each); when both fit
     the encoder's max_batch they go through it as ONE call, otherwise as two."""
     n, single = check_frames(frames, encoder.frame_layout, encoder.channels, encoder.frame_size)
     if check_frames(goal_frames, encoder.frame_layout, encoder.channels, encoder.frame_size) != (n, single):
         raise ValueError("frames and goal_frames must have the same shape, got %s and %s" % (tuple(frames.shape), tuple(goal_frames.shape)))
     if "goal" in plan_kwargs:
         raise ValueError("reach takes the goal as goal_frames")
+    if planner not in ("cem", "search"):
+        raise ValueError("planner must be 'cem' or 'search', got %r" % (planner,))
     # Host frames are uploaded here, with a copy that has ended when it returns: the encoder's pinned staging buffer is refilled by
     # the host at every call, and two calls back to back would refill it while the first call's copy to the device may still wait
     # on the stream.  A device tensor is read by the encoder in place.
@@ -1598,4 +1777,6 @@ def reach(encoder, dynamics, frames, goal_frames, horizon, **plan_kwargs):
     else:
         states = encoder(dev[0].contiguous()).clone()  # (the encoder's state buffer is reused by the next call)
         goals = encoder(dev[1].contiguous())
+    if planner == "search":
+        return dynamics.search(states, horizon, goal=goals, **plan_kwargs)
     return dynamics.plan(states, horizon, goal=goals, **plan_kwargs)

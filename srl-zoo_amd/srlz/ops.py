@@ -2458,6 +2458,62 @@ def plan_cem_goal(states, wf, bf, reward, goal, n_plans, horizon, iterations, el
 
 
 # ----------------------------------------------------------------------------------------------------------------
+# Deployment tree search (csrc/beam.hip): exact enumeration or a beam over the action sequences of the dynamics above, one launch per
+# level, all of them enqueued here back to back (include/srlz.h states the algorithm).  Thin, as plan_cem: the caller owns every
+# buffer, nothing is allocated and no autograd node is made.
+# ----------------------------------------------------------------------------------------------------------------
+def beam_supported(s, a, h, n_rewards, has_reward, beam, horizon):
+    return bool(C.beam_supported(int(s), int(a), int(h), int(n_rewards), int(bool(has_reward)), int(beam), int(horizon)))
+
+
+def beam_workspace(n, beam, horizon, s, a):
+    """Bytes of workspace of a beam_search call; 0 for a shape it refuses."""
+    return int(C.beam_workspace(int(n), int(beam), int(horizon), int(s), int(a)))
+
+
+def beam_leaves(beam, a, horizon):
+    """L: the leaves a beam_search call keeps per environment; 0 outside the limits."""
+    return int(C.beam_leaves(int(beam), int(a), int(horizon)))
+
+
+def beam_search(states, wf, bf, reward, beam, horizon, best_plan, best_return, workspace, gamma=1.0, leaf_plans=None, leaf_returns=None,
+                goal=None, goal_weight=1.0, goal_mode="running"):
+    """`horizon` launches of beam_level_kernel.  states fp32 [N,S]; wf / bf / reward = (w1 .. b3) as rollout takes them (reward may be
+    None with a goal); goal None, or as rollout_goal takes it.  Outputs best_plan int32 [N,T], best_return fp32 [N]; leaf_plans int32
+    [N,L,T] and leaf_returns fp32 [N,L] keep the leaves (both or neither), L = beam_leaves(beam, A, horizon); workspace: a uint8
+    device tensor of beam_workspace(...) bytes."""
+    states = _rollout_f32(states, "states")
+    if states.dim() != 2:
+        raise C.SrlzError("beam_search: states [N,S] expected, got %s" % (tuple(states.shape),))
+    n, s = states.shape
+    wf = _rollout_f32(wf, "forward_net.weight")
+    if wf.dim() != 2 or wf.shape[0] != s or wf.shape[1] <= s:
+        raise C.SrlzError("beam_search: forward_net.weight of shape %s does not take states of %d dimensions" % (tuple(wf.shape), s))
+    a = wf.shape[1] - s
+    bf = _rollout_f32(bf, "forward_net.bias", (s,))
+    gstride, mode = 0, 0
+    if goal is not None:
+        goal, gstride, mode = _goal_args(goal, n, s, goal_mode, "beam_search")
+    h, head = 0, (None,) * 6
+    if reward is not None:
+        h = reward[0].shape[0]
+        shapes = ((h, 2 * s), (h,), (h, h), (h,), (2, h), (2,))
+        head = tuple(_rollout_f32(p, "reward_net parameter", shape) for p, shape in zip(reward, shapes))
+    w, t = int(beam), int(horizon)
+    leaves = beam_leaves(w, a, t)
+    best_plan = _plan_buf(best_plan, "best_plan", torch.int32, (n, t))
+    best_return = _plan_buf(best_return, "best_return", torch.float32, (n,))
+    leaf_plans = _plan_buf(leaf_plans, "leaf_plans", torch.int32, (n, leaves, t))
+    leaf_returns = _plan_buf(leaf_returns, "leaf_returns", torch.float32, (n, leaves))
+    if workspace is None or workspace.dtype != torch.uint8 or not workspace.is_cuda or not workspace.is_contiguous():
+        raise C.SrlzError("beam_search: workspace must be a contiguous uint8 device tensor")
+    C.beam_search(ptr(states), ptr(wf), ptr(bf), *[ptr(p) for p in head], ptr(best_plan), ptr(best_return), ptr(leaf_plans),
+                  ptr(leaf_returns), ptr(workspace), workspace.numel(), n, w, t, s, a, h, 2, float(gamma), ptr(goal), gstride,
+                  float(goal_weight), mode, stream())
+    return best_plan
+
+
+# ----------------------------------------------------------------------------------------------------------------
 # The k-step error of the dynamics on a recorded sequence (csrc/horizon.hip; include/srlz.h states the rule): two launches.  Thin,
 # as rollout: the caller (srlz/deploy.py) owns every buffer and checks the contract starts[r] + len[r] <= N - 1, 0 <= len[r] <= T.
 # ----------------------------------------------------------------------------------------------------------------
