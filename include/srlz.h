@@ -1137,6 +1137,43 @@ int srlz_horizon_sums(const float* err, const float* base, const float* reward_l
                       srlz_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The forward head in closed form (csrc/dynfit.hip; srlz/dynfit.py, evaluation/predict_forward.py --fit): the normal equations of
+ *   next_state = state + self.forward_net(th.cat((state, encodeOneHot(action, self.action_dim)), dim=1))
+ *                                                                                         models/forward_inverse.py:16,30-31
+ * under the MSE of losses/losses.py:forwardModelLoss, over M recorded transitions.  states fp32 [N,S], actions int32 [N]
+ * (actions[i] leads from frame i to i + 1), starts int32 [M] on the device: transition m is the frame pair (i, i + 1), i = starts[m].
+ * In fp64, with P = S + A + 1:
+ *   z_i = [ (double)s_i[0..S) | onehot(a_i)[0..A) | 1 ]        y_i = (double)s_{i+1} - (double)s_i
+ *   G [P,P] = sum_m z zᵀ          C [P,S] = sum_m z yᵀ
+ * The conversions are exact and the subtraction is an fp64 one.  Neither [z | y] nor the one-hot block is ever in memory: a stage
+ * of 32 transitions is built in LDS (coalesced loads of s_i and s_{i+1}) and its 16-wide column tiles feed
+ * v_mfma_f64_16x16x4_f64, the MFMA's k index running over the transitions.  Only the lower triangle of G's 16 x 16 tiles and C are
+ * computed.  An action outside [0, A) gives a zero one-hot block for its transition (the Python layer refuses it on the host).
+ * Order of every sum, a function of (M, S, A) alone: the transitions are split into chunks of srlz_dynfit_chunk_rows(M, S, A)
+ * consecutive entries of starts (a multiple of 32), one workgroup per chunk and group of 8 tiles; inside a chunk wave w of four
+ * accumulates the quads of transitions w, w + 4, .. in ascending order, the four waves are added ((w0 + w1) + w2) + w3 and the
+ * partial tile goes to ws; a second launch adds the partials in chunk order and writes G's upper triangle as a copy of the lower
+ * one.  No atomics, plain vector stores: G is exactly symmetric, two calls leave identical bits, and every element of G and C is
+ * written exactly once and nothing beyond them.
+ * Limits (srlz_dynfit_supported): 1 <= S <= 512, the width of the dynamics kernels' state tile (srlz_rollout_supported), and
+ * 1 <= A <= 64.  They bound the system at P <= 577 — 1887 output tiles, one launch's grid — which the host solves in fp64 in well
+ * under a second, and they leave 8 chunks within the workspace cap at the largest shape.
+ * Workspace: tiles * chunks * 2048 bytes, with at most 256 chunks and at most 16384 partial tiles: never more than 32 MiB, whatever
+ * M.  srlz_dynfit_chunk_rows and srlz_dynfit_workspace are functions of the shapes alone and return 0 for a shape the launcher
+ * rejects (M < 1 or an unsupported (S, A)).
+ * starts_host is the SAME table on the host: every entry is checked there against [0, N - 2] before anything is launched, as
+ * srlz_reward_probe_fit checks its table (the device copy is clamped to that range, so it never forms an address outside states).
+ * Refused before any launch, nothing written: an unsupported (S, A), N < 2, M < 1, N * S >= 2^31, a start outside [0, N - 2]:
+ * SRLZ_ERR_BAD_DESC; a missing pointer SRLZ_ERR_NULL; ws_bytes < srlz_dynfit_workspace(M, S, A) SRLZ_ERR_WORKSPACE.
+ * ------------------------------------------------------------------------------------------------------------ */
+int srlz_dynfit_supported(int S, int A);
+int srlz_dynfit_chunk_rows(int M, int S, int A);
+size_t srlz_dynfit_workspace(int M, int S, int A);
+int srlz_dynfit_gram(const float* states /*[N,S]*/, const int* actions /*[N]*/, const int* starts /*[M]*/,
+                     const int* starts_host /*[M]*/, int N, int M, int S, int A, double* G /*[P,P]*/, double* C /*[P,S]*/, void* ws,
+                     size_t ws_bytes, srlz_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Debug / calibration hooks (not on the product path).
  * ------------------------------------------------------------------------------------------------------------ */
 /* Host-only: dump the virtual-grid program of a 64->64 convolution (tests interpret it on the CPU).

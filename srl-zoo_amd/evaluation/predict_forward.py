@@ -12,6 +12,18 @@ folder named in exp_config.json, the model through srlz.deploy.LatentDynamics.fr
 <log folder>/forward_horizon.json written: horizon, count, mse, baseline_mse, ratio (below 1: the model beats "nothing moves"),
 reward_accuracy, majority_accuracy (null without a trained reward head).  DESIGN.md §3.18.
 
+    python -m evaluation.predict_forward --log-folder logs/<dataset>/<experiment>/ --fit [-i states_rewards.npz | --ground-truth]
+                                         [--ridge 1e-6] [--val-fraction 0.2] [--seed 0] [--horizon 10]
+
+With --fit no model is loaded: the question is whether a LINEAR forward model is predictable in the space of these states — PCA
+states, supervised or ground-truth states, a model trained without the forward loss.  The head is fitted in closed form
+(srlz.dynfit) on the training episodes of srlz.dynfit.split_episodes(episode_starts, --val-fraction, --seed), and
+the k-step error is measured twice, on the validation transitions (the printed lines) and on the training ones.  The states come
+from -i, else from the log folder's states_rewards.npz, or with --ground-truth from the dataset's true states, as predict_reward
+takes them without -i.  <log folder>/forward_horizon_fit.json holds the keys above for the validation side, the same keys under
+"train", and "fit": ridge, count, val_fraction, seed, route, state_dim, n_actions.  --ground-truth, --ridge, --val-fraction and
+--seed without --fit are an error.
+
 There is no reference counterpart: the reference has no metric for its dynamics heads.  --no-cuda, or a machine without a GPU,
 raises: this build has no CPU fallback.
 """
@@ -28,11 +40,33 @@ from srlz._cabi import SrlzError
 from utils import parseDataFolder, loadData
 
 OUTPUT = "forward_horizon.json"
+OUTPUT_FIT = "forward_horizon_fit.json"
+FIT_KEYS = ("ridge", "count", "val_fraction", "seed", "route", "state_dim", "n_actions")
+FIT_DEFAULTS = (("ridge", 1e-6), ("val_fraction", 0.2), ("seed", 0))  # what --fit uses for a flag that was not given
 KEYS = ("horizon", "count", "mse", "baseline_mse", "ratio", "reward_accuracy", "majority_accuracy")
 
 
+class _Parser(argparse.ArgumentParser):
+    """The flags of --fit are refused without it, and take their defaults with it."""
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super(_Parser, self).parse_args(args, namespace)
+        if not ns.fit:
+            given = [flag for flag, on in (("--ground-truth", ns.ground_truth), ("--ridge", ns.ridge is not None),
+                                           ("--val-fraction", ns.val_fraction is not None), ("--seed", ns.seed is not None)) if on]
+            if given:
+                self.error("{} only with --fit".format(", ".join(given)))
+            return ns
+        if ns.ground_truth and ns.input_file != "":
+            self.error("--ground-truth and -i name two sources of states: give one")
+        for name, default in FIT_DEFAULTS:
+            if getattr(ns, name) is None:
+                setattr(ns, name, default)
+        return ns
+
+
 def build_parser():
-    parser = argparse.ArgumentParser(description='k-step prediction error of the forward model on the recorded dataset')
+    parser = _Parser(description='k-step prediction error of the forward model on the recorded dataset')
     parser.add_argument('--log-folder', type=str, required=True, help='Experiment folder (exp_config.json, srl_model.pth)')
     parser.add_argument('--data-folder', type=str, default="", help='Dataset folder (default: the one named in exp_config.json)')
     parser.add_argument('-i', '--input-file', type=str, default="",
@@ -41,6 +75,14 @@ def build_parser():
     parser.add_argument('--training-set-size', type=int, default=-1,
                         help='Limit size (number of samples) of the evaluated set (default: -1)')
     parser.add_argument('--no-cuda', action='store_true', default=False, help='refused: there is no CPU path')
+    parser.add_argument('--fit', action='store_true', default=False,
+                        help='fit the forward head to the states in closed form instead of loading srl_model.pth')
+    parser.add_argument('--ridge', type=float, default=None, help='with --fit: the penalty on the weights (default: 1e-6)')
+    parser.add_argument('--val-fraction', type=float, default=None,
+                        help='with --fit: the share of the episodes held out for validation (default: 0.2)')
+    parser.add_argument('--seed', type=int, default=None, help='with --fit: the seed of the episode split (default: 0)')
+    parser.add_argument('--ground-truth', action='store_true', default=False,
+                        help="with --fit: take the dataset's true states instead of a states file")
     return parser
 
 
@@ -58,12 +100,16 @@ def prepare(args):
         with open(os.path.join(log_folder, "exp_config.json"), "r") as f:
             data_folder = json.load(f)["data-folder"]
     print('Loading data ... ')
-    training_data, _, _, _ = loadData(parseDataFolder(data_folder))
+    training_data, _, true_states, _ = loadData(parseDataFolder(data_folder))
     actions, rewards = np.asarray(training_data['actions']).reshape(-1), np.asarray(training_data['rewards']).reshape(-1)
     episode_starts = np.asarray(training_data['episode_starts']).reshape(-1)
-    input_file = args.input_file if args.input_file != "" else os.path.join(log_folder, "states_rewards.npz")
-    print("Loading {}...".format(input_file))
-    states = np.load(input_file)['states']
+    if getattr(args, "ground_truth", False):
+        print("Using ground truth")
+        states = np.asarray(true_states)
+    else:
+        input_file = args.input_file if args.input_file != "" else os.path.join(log_folder, "states_rewards.npz")
+        print("Loading {}...".format(input_file))
+        states = np.load(input_file)['states']
     limit = min(len(states), len(actions))
     if args.training_set_size > 0:
         limit = min(limit, args.training_set_size)
@@ -83,10 +129,43 @@ def report(result):
     return lines
 
 
+def run_fit(args):
+    """--fit: the head fitted on the training episodes, the k-step error on the validation and on the training transitions."""
+    states, actions, _, episode_starts = prepare(args)
+    from srlz import dynfit
+    from srlz.deploy import LatentDynamics
+    states = np.asarray(states, np.float32)
+    if states.ndim != 2:
+        raise ValueError("the states must be [N,S], got shape {}".format(states.shape))
+    train, val = dynfit.split_episodes(episode_starts, args.val_fraction, args.seed)
+    everyone = np.concatenate((train, val))
+    n_actions = int(np.asarray(actions)[everyone].max()) + 1  # (an action the training episodes never took still has its column)
+    dyn = LatentDynamics.from_recording(states, actions, episode_starts, n_actions=n_actions, ridge=args.ridge, starts=train,
+                                        max_horizon=max(32, args.horizon))
+    fit = dyn.fit
+    on_val = dyn.horizon_error(states, actions, episode_starts, args.horizon, starts=val)
+    on_train = dyn.horizon_error(states, actions, episode_starts, args.horizon, starts=train)
+    print("Open-loop error of the fitted forward head over {} steps on {} validation transitions ({} fitted, fit route {}, route {})"
+          .format(args.horizon, len(val), fit.count, fit.route, dyn.route))
+    for line in report(on_val):
+        print(line)
+    out = on_val.as_dict()
+    out["train"] = on_train.as_dict()
+    out["fit"] = {"ridge": fit.ridge, "count": fit.count, "val_fraction": args.val_fraction, "seed": args.seed, "route": fit.route,
+                  "state_dim": fit.state_dim, "n_actions": fit.n_actions}
+    log_folder = args.log_folder if args.log_folder.endswith("/") else args.log_folder + "/"
+    with open(os.path.join(log_folder, OUTPUT_FIT), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    return out
+
+
 def run(args):
     requireGpu(args)
     if args.horizon < 1:
         raise ValueError("--horizon must be at least 1, got {}".format(args.horizon))
+    if getattr(args, "fit", False):
+        return run_fit(args)
     states, actions, rewards, episode_starts = prepare(args)
     from srlz.deploy import LatentDynamics
     dyn = LatentDynamics.from_log_folder(args.log_folder, max_horizon=max(32, args.horizon))
@@ -104,7 +183,7 @@ def run(args):
 
 
 def main(argv=None):
-    """:return: the dictionary written to forward_horizon.json"""
+    """:return: the dictionary written to forward_horizon.json (--fit: forward_horizon_fit.json)"""
     return run(build_parser().parse_args(argv))
 
 

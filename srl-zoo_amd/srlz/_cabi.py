@@ -294,6 +294,10 @@ _PROTOS = {
     "srlz_horizon_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "srlz_horizon_rows": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "srlz_horizon_sums": (c_int, [P, P, P, P, P, P, c_int, c_int, P, P, P, P, P]),
+    "srlz_dynfit_supported": (c_int, [c_int, c_int]),
+    "srlz_dynfit_chunk_rows": (c_int, [c_int, c_int, c_int]),
+    "srlz_dynfit_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "srlz_dynfit_gram": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P]),
 }
 
 # entry points whose int return value is data, not a status
@@ -308,7 +312,8 @@ _NOT_STATUS = {"srlz_version", "srlz_device_cus", "srlz_conv64_fwd_tiles", "srlz
                "srlz_infer_tile", "srlz_conv64_bwd_fused_workgroups", "srlz_conv1_workgroups",
                "srlz_conv1_buffer_staging_supported", "srlz_infer_dec_supported", "srlz_infer_dec_tile", "srlz_rollout_supported",
                "srlz_rollout_tile", "srlz_plan_supported", "srlz_rollout_goal_supported", "srlz_plan_goal_supported",
-               "srlz_horizon_supported", "srlz_beam_supported", "srlz_beam_leaves"}
+               "srlz_horizon_supported", "srlz_beam_supported", "srlz_beam_leaves", "srlz_dynfit_supported",
+               "srlz_dynfit_chunk_rows"}
 
 EXPORTED = sorted(_PROTOS.keys())
 

@@ -641,6 +641,12 @@ def reconstruct(encoder, decoder, frames):
 # two launches of csrc/horizon.hip (include/srlz.h states every sum's order): the imagined states never leave the chip, and max_rows
 # does not apply — nothing is staged per row.  Route "model" is the model's own forwardModel / rewardModel step by step with fp64
 # sums on the host: SRLModulesSplit, head shapes srlz_horizon_supported refuses, horizons beyond 32 or max_horizon.
+#
+# A forward head without training.  The head is one Linear under an MSE: over a recording its minimiser is a linear solve
+# (srlz/dynfit.py, csrc/dynfit.hip), so any representation with recorded actions can be rolled, planned and measured:
+#     dyn = LatentDynamics.from_recording(states, actions, episode_starts, n_actions=None, ridge=1e-6, starts=None)
+#     fit = dyn.refit_forward(states, actions, episode_starts, ridge=1e-6, starts=None)     # a model's own head, in place
+#     fit.weight, fit.bias, fit.weight64, fit.bias64, fit.count, fit.gram, fit.cross, fit.route
 # =============================================================================================================
 ROUTE_ROLLOUT = "rollout"
 HEADS = ("forward", "inverse", "reward")
@@ -1205,6 +1211,7 @@ class LatentDynamics(object):
         self._goal_bufs = {}  # the goal calls' device buffers: made by the first call with a goal
         self._search_bufs = {}  # the tree search's device buffers: made by the first search call
         self._forced_model = route is not None
+        self.fit = None  # the ForwardFit of the last refit_forward / from_recording
         self.device = next(self.owner.forward_net.parameters()).device
         if self.device.type != "cuda":
             raise C.SrlzError("LatentDynamics: the model must live on the GPU (there is no CPU path)")
@@ -1239,7 +1246,54 @@ class LatentDynamics(object):
         """The route of the most recent call; before any call, the route that calls within max_rows and max_horizon take."""
         return self.last_route or self._route
 
+    @classmethod
+    def from_recording(cls, states, actions, episode_starts, n_actions=None, ridge=1e-6, starts=None, max_rows=8192, max_horizon=32):
+        """Dynamics for a representation that has no network behind it (PCA, supervised or ground-truth states, a model trained
+        without the forward loss): the three heads alone (srlz.dynfit.heads_only_modules, losses = ["forward"], no encoder), the
+        forward head fitted to the recording in closed form (srlz.dynfit.fit_forward; the arguments are its own).  The route is the
+        one a trained model of these dimensions takes.  The reward and inverse heads are untrained and stay unused: goal= planning
+        works on the distance term alone.  The fit is kept as .fit."""
+        from . import dynfit
+        from models.learner import _requireGpu
+        _requireGpu(True)
+        fit = dynfit.fit_forward(states, actions, episode_starts, n_actions=n_actions, ridge=ridge, starts=starts)
+        model = dynfit.heads_only_modules(fit.state_dim, fit.n_actions).to(torch.device("cuda", torch.cuda.current_device()))
+        model.eval()
+        dyn = cls(model, max_rows=max_rows, max_horizon=max_horizon)
+        dyn._install_fit(fit)
+        return dyn
+
+    def _install_fit(self, fit):
+        fw = self.owner.forward_net
+        with torch.no_grad():
+            fw.weight.copy_(torch.from_numpy(fit.weight))
+            fw.bias.copy_(torch.from_numpy(fit.bias))
+        if "forward" not in self.heads:
+            self.heads = tuple(h for h in HEADS if h in self.heads or h == "forward")
+        self.fit = fit
+
+    def refit_forward(self, states, actions, episode_starts, ridge=1e-6, starts=None):
+        """Fit the forward head to a recorded sequence in closed form (srlz.dynfit.fit_forward, n_actions = the head's) and copy the
+        solution into owner.forward_net IN PLACE, under no_grad -> the ForwardFit.  "forward" joins self.heads, whatever the model's
+        losses trained.  Nothing has to be refreshed: the rollout, plan, beam and horizon launches take forward_net.weight / .bias
+        by address at every call and route "model" calls the owner's forwardModel, so the next call of any kind uses the new head;
+        this object keeps no copy of the weights.  (A StateEncoder or FrameDecoder of the same model is not concerned: the heads
+        are not theirs.)  ValueError when the recording's state_dim is not the head's, or when a listed transition holds an action
+        outside the head's [0, n_actions); fit_forward's other ValueErrors as they are."""
+        from . import dynfit
+        if not isinstance(states, (np.ndarray, torch.Tensor)) or len(states.shape) != 2 or states.shape[1] != self.state_dim:
+            raise ValueError("the recording's states of shape %s do not match the head's state_dim = %d"
+                             % (tuple(getattr(states, "shape", ())), self.state_dim))
+        fw = self.owner.forward_net
+        if fw.bias is None:
+            raise ValueError("refit_forward needs a forward head with a bias")
+        fit = dynfit.fit_forward(states, actions, episode_starts, n_actions=self.n_actions, ridge=ridge, starts=starts)
+        self._install_fit(fit)
+        return fit
+
     def _need(self, head):
+        if head in self.heads:  # (refit_forward adds "forward" to the heads the losses trained)
+            return
         check_head(self.owner, head, self.untrained_ok)
 
     def _uses_reward(self):

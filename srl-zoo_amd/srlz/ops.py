@@ -2583,3 +2583,50 @@ def horizon_sums(err, base, starts, lens, count, sum_err, sum_base, reward_logit
     C.horizon_sums(ptr(err), ptr(base), ptr(reward_logits), ptr(labels), ptr(starts), ptr(lens), m, t, ptr(count), ptr(sum_err),
                    ptr(sum_base), ptr(hits), stream())
     return count, sum_err, sum_base, hits
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# The forward head's normal equations on a recorded sequence (csrc/dynfit.hip; include/srlz.h states every sum's order): two
+# launches.  Thin, as horizon_rows: the caller (srlz/dynfit.py) owns the data and has checked the actions on the host; the table of
+# transitions is checked by the launcher itself, on its host copy.
+# ----------------------------------------------------------------------------------------------------------------
+def dynfit_supported(s, a):
+    return bool(C.dynfit_supported(int(s), int(a)))
+
+
+def dynfit_chunk_rows(m, s, a):
+    return int(C.dynfit_chunk_rows(int(m), int(s), int(a)))
+
+
+def dynfit_workspace(m, s, a):
+    return int(C.dynfit_workspace(int(m), int(s), int(a)))
+
+
+def dynfit_gram(states, actions, starts, n_actions, gram=None, cross=None, workspace=None):
+    """srlz_dynfit_gram: states fp32 [N,S] and actions int32 [N] on the device, starts int32 [M] on the HOST (checked there against
+    [0, N - 2], then uploaded) -> (G fp64 [P,P], C fp64 [P,S]) on the device, P = S + n_actions + 1.  gram / cross / workspace: the
+    caller's buffers (a uint8 workspace of at least dynfit_workspace(M, S, A) bytes), made here when None."""
+    states = _rollout_f32(states, "states")
+    if states.dim() != 2:
+        raise C.SrlzError("dynfit: states [N,S] expected, got %s" % (tuple(states.shape),))
+    n, s = states.shape
+    a = int(n_actions)
+    if not dynfit_supported(s, a):
+        raise C.SrlzError("dynfit: state_dim %d with %d actions is outside srlz_dynfit_supported" % (s, a))
+    actions = _horizon_t(actions, "actions", torch.int32, (n,))
+    if not torch.is_tensor(starts) or starts.device.type != "cpu" or starts.dtype != torch.int32 or starts.dim() != 1 \
+            or not starts.is_contiguous() or starts.shape[0] < 1:
+        raise C.SrlzError("dynfit: starts must be a non-empty contiguous int32 host tensor [M] (it is checked on the host, then uploaded)")
+    m, p = int(starts.shape[0]), s + a + 1
+    dev = states.device
+    gram = torch.empty((p, p), dtype=torch.float64, device=dev) if gram is None else _horizon_t(gram, "gram", torch.float64, (p, p))
+    cross = torch.empty((p, s), dtype=torch.float64, device=dev) if cross is None else _horizon_t(cross, "cross", torch.float64, (p, s))
+    nbytes = dynfit_workspace(m, s, a)
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or not workspace.is_cuda or not workspace.is_contiguous():
+        raise C.SrlzError("dynfit: workspace must be a contiguous uint8 device tensor")
+    d_starts = starts.to(dev)
+    C.dynfit_gram(ptr(states), ptr(actions), ptr(d_starts), ctypes.c_void_p(starts.data_ptr()), n, m, s, a, ptr(gram), ptr(cross),
+                  ptr(workspace), workspace.numel(), stream())
+    return gram, cross
