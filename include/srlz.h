@@ -1174,6 +1174,64 @@ int srlz_dynfit_gram(const float* states /*[N,S]*/, const int* actions /*[N]*/, 
                      size_t ws_bytes, srlz_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The reward head fitted on a recording (csrc/headfit.hip; srlz/headfit.py, LatentDynamics.refit_reward,
+ * evaluation/predict_forward.py --fit --fit-reward).  Replaces the reward part of the learner's minibatch loop,
+ *   reward_pred = model.rewardModel(states, next_states); rewardModelLoss(...) -> nn.CrossEntropyLoss; loss.backward();
+ *   optimizer.step()                                       models/learner.py:444-449, losses/losses.py:158
+ * with the classifier Linear(2S,H)-ReLU-Linear(H,H)-ReLU-Linear(H,2) on th.cat((state, next_state), dim=1)
+ *                                                                                         models/forward_inverse.py:78-95
+ * by ONE launch per training epoch (srlz_headfit_fit) and ONE per validation phase (srlz_headfit_eval).  The general form of
+ * srlz_reward_probe_* (H = 4), which keep their own bits.
+ *   states [N, S] fp32 and labels [N] int32 (class 1 where the label is 1, class 0 otherwise: a compare, nothing is indexed by a
+ *   label) stay on the device.  idx [n, B] int32 on the device, idx_host the SAME table on the host: every entry is checked there
+ *   against [0, N - 2] before anything is launched; the device copy is clamped to that range as it is read, so no address outside
+ *   states is ever formed.  Row b of minibatch s is the 2S floats at states + idx[s][b] * S, i.e. the rows i and i + 1 — the
+ *   concatenation is never written; its label is labels[idx[s][b]].
+ *   params / m / v / last_grad: srlz_headfit_n_params(S, H) = 2S*H + H + H*H + H + 2*H + 2 floats each in state_dict order
+ *   (reward_net.0.weight [H, 2S], 0.bias, 2.weight [H, H], 2.bias, 4.weight [2, H], 4.bias).
+ *   running_loss [1] fp64 and counts [5] int64 (correct, correct of class 0, of class 1, rows of class 0, of class 1) are ADDED TO.
+ *   Argmax ties go to class 0, as th.max does.
+ * fit: n_steps consecutive Adam steps (torch's defaults are the caller's to pass; the arithmetic of srlz_adam_step) in one launch
+ *   of one persistent workgroup of 256 threads.  Parameters and gradient stay in LDS from the first step to the last; the Adam
+ *   moments m and v stay in GLOBAL memory in state_dict order, read and written once per step (two more copies in LDS would halve
+ *   the envelope).  Step s uses the bias corrections of t = t0 + s + 1.  Forward in fp32, cross-entropy as the mean over B in
+ *   log-sum-exp form; no gradient into the states.  Rows are processed in chunks of srlz_headfit_chunk_rows(S, H).  Order of every
+ *   sum, a function of (S, H, B) alone: layer 1 — 16 lanes per row, lane kk adds k = kk, kk + 16, .. ascending, then a butterfly
+ *   over the 16 lanes (offsets 8, 4, 2, 1); layers 2 and 3 and their transposes — one thread per output, the index ascending from
+ *   the bias; every parameter's gradient — one thread per element, rows in row order, chunk after chunk; the loss — per chunk, lane
+ *   l of one wave adds rows l, l + 64 in fp64, then a butterfly, chunks in order.  running_loss += (sum of row losses / B) * B per
+ *   step in fp64; step_loss (may be NULL) receives the n_steps mean losses; last_grad (may be NULL) the gradient of the LAST step.
+ *   No float atomics, plain vector stores.  Two calls leave identical bits; n steps in one call and n calls of one step leave
+ *   identical bits in params, m, v, running_loss, counts and step_loss.
+ * eval: the same forward over n_batches * B independent rows, 64 per workgroup, the row loss in fp64; per-workgroup sums go to ws
+ *   (srlz_headfit_eval_workspace(n_batches, B) bytes) and are added in workgroup order by the workgroup that finishes last
+ *   (`ticket`: one zeroed unsigned the kernel leaves zeroed; no spinning, no grid barrier); counts by integer atomics.  params are
+ *   only read.
+ * Limits.  With K = 2S, HP = H rounded up to a multiple of 4, HPAD = HP | 4, the LDS image of the parameters holds
+ *   PL = (K + H + 4) * HPAD + 4 floats (W1 as [k][HPAD], b1, W2 transposed, b2, W3, b3; pads zero) and a row of a chunk costs
+ *   (K | 1) + 4 * HPAD + 7 floats (the row, its record d a1 | h1 | d a2 | h2 | dz, loss, flag, label).
+ *   srlz_headfit_chunk_rows(S, H) = min(128, floor((40956 - 2 * PL - 512) / ((K | 1) + 4 * HPAD + 7))), and 0 where that is below 16
+ *   or (S, H) lies outside [1, 512] x [1, 32];  srlz_headfit_supported(S, H) = srlz_headfit_chunk_rows(S, H) > 0.
+ *   That accepts every S <= 200 with H <= 16 (S = 200, H = 16: 67,232 bytes of parameters and gradient, chunks of 48 rows,
+ *   162,976 bytes in all), S <= 512 up to H = 4, S <= 489 up to H = 12, S <= 341 up to H = 16, S <= 256 up to H = 24 and
+ *   S <= 201 at H = 32.
+ * Refused before anything is enqueued, nothing written: an unsupported (S, H), N < 2, n < 1, B < 1, N * S >= 2^31, n * B >= 2^31,
+ *   t0 < 0, an entry of idx_host outside [0, N - 2]: SRLZ_ERR_BAD_DESC; a missing pointer SRLZ_ERR_NULL; ws_bytes below
+ *   srlz_headfit_eval_workspace: SRLZ_ERR_WORKSPACE.  srlz_headfit_eval_workspace returns 0 for n_batches < 1, B < 1 or 2^31 rows.
+ * ------------------------------------------------------------------------------------------------------------ */
+int srlz_headfit_supported(int S, int H);
+long long srlz_headfit_n_params(int S, int H); /* 0 for S < 1 or H < 1 */
+int srlz_headfit_chunk_rows(int S, int H);     /* rows of a chunk; 0 for a shape the launchers reject */
+int srlz_headfit_fit(const float* states /*[N,S]*/, const int* labels /*[N]*/, int N, int S, int H, const int* idx /*[n_steps,B]*/,
+                     const int* idx_host /*[n_steps,B]*/, int n_steps, int B, float* params, float* m, float* v, int t0, double lr,
+                     double beta1, double beta2, double eps, double* running_loss /*[1]*/, long long* counts /*[5]*/,
+                     double* step_loss /*[n_steps] or NULL*/, float* last_grad /*[P] or NULL*/, srlz_stream_t stream);
+size_t srlz_headfit_eval_workspace(int n_batches, int B);
+int srlz_headfit_eval(const float* states /*[N,S]*/, const int* labels /*[N]*/, int N, int S, int H, const int* idx /*[n_batches,B]*/,
+                      const int* idx_host /*[n_batches,B]*/, int n_batches, int B, const float* params, double* running_loss /*[1]*/,
+                      long long* counts /*[5]*/, void* ws, size_t ws_bytes, unsigned* ticket, srlz_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Debug / calibration hooks (not on the product path).
  * ------------------------------------------------------------------------------------------------------------ */
 /* Host-only: dump the virtual-grid program of a 64->64 convolution (tests interpret it on the CPU).

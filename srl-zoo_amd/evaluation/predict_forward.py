@@ -24,6 +24,17 @@ takes them without -i.  <log folder>/forward_horizon_fit.json holds the keys abo
 "train", and "fit": ridge, count, val_fraction, seed, route, state_dim, n_actions.  --ground-truth, --ridge, --val-fraction and
 --seed without --fit are an error.
 
+    python -m evaluation.predict_forward --log-folder logs/<dataset>/<experiment>/ --fit --fit-reward
+                                         [--reward-epochs 30] [--reward-batch-size 32] [--reward-lr 0.005]
+
+With --fit --fit-reward the reward head is fitted too (srlz.headfit, DESIGN.md §3.21: Adam, one launch per epoch, on four fifths of
+the training episodes, the epoch with the lowest loss on the remaining fifth kept — srlz.headfit.split_starts(train, ., 0.2, --seed);
+the validation episodes take no part in it) and asked, on the imagined pairs, for the recorded
+rewards: is the reward predictable from (s, s') in this space, on held-out episodes?  The printed lines and both sides of the JSON
+gain reward_accuracy / majority_accuracy, and the JSON one object "reward_fit": route, hidden, epochs, batch_size, lr, seed,
+best_epoch, count, val_count (the two shares of the training transitions) and the per-epoch train_loss, val_loss, train_accuracy, val_accuracy.  "fit" keeps its keys.
+--fit-reward without --fit, and the --reward-* flags without --fit-reward, are an error.
+
 There is no reference counterpart: the reference has no metric for its dynamics heads.  --no-cuda, or a machine without a GPU,
 raises: this build has no CPU fallback.
 """
@@ -43,6 +54,7 @@ OUTPUT = "forward_horizon.json"
 OUTPUT_FIT = "forward_horizon_fit.json"
 FIT_KEYS = ("ridge", "count", "val_fraction", "seed", "route", "state_dim", "n_actions")
 FIT_DEFAULTS = (("ridge", 1e-6), ("val_fraction", 0.2), ("seed", 0))  # what --fit uses for a flag that was not given
+REWARD_DEFAULTS = (("reward_epochs", 30), ("reward_batch_size", 32), ("reward_lr", 0.005))  # train.py's own, with --fit-reward
 KEYS = ("horizon", "count", "mse", "baseline_mse", "ratio", "reward_accuracy", "majority_accuracy")
 
 
@@ -51,9 +63,16 @@ class _Parser(argparse.ArgumentParser):
 
     def parse_args(self, args=None, namespace=None):
         ns = super(_Parser, self).parse_args(args, namespace)
+        if not ns.fit_reward:
+            given = [flag for flag, on in (("--reward-epochs", ns.reward_epochs is not None),
+                                           ("--reward-batch-size", ns.reward_batch_size is not None),
+                                           ("--reward-lr", ns.reward_lr is not None)) if on]
+            if given:
+                self.error("{} only with --fit-reward".format(", ".join(given)))
         if not ns.fit:
             given = [flag for flag, on in (("--ground-truth", ns.ground_truth), ("--ridge", ns.ridge is not None),
-                                           ("--val-fraction", ns.val_fraction is not None), ("--seed", ns.seed is not None)) if on]
+                                           ("--val-fraction", ns.val_fraction is not None), ("--seed", ns.seed is not None),
+                                           ("--fit-reward", ns.fit_reward)) if on]
             if given:
                 self.error("{} only with --fit".format(", ".join(given)))
             return ns
@@ -62,6 +81,10 @@ class _Parser(argparse.ArgumentParser):
         for name, default in FIT_DEFAULTS:
             if getattr(ns, name) is None:
                 setattr(ns, name, default)
+        if ns.fit_reward:
+            for name, default in REWARD_DEFAULTS:
+                if getattr(ns, name) is None:
+                    setattr(ns, name, default)
         return ns
 
 
@@ -83,6 +106,12 @@ def build_parser():
     parser.add_argument('--seed', type=int, default=None, help='with --fit: the seed of the episode split (default: 0)')
     parser.add_argument('--ground-truth', action='store_true', default=False,
                         help="with --fit: take the dataset's true states instead of a states file")
+    parser.add_argument('--fit-reward', action='store_true', default=False,
+                        help='with --fit: fit the reward head too (Adam, one launch per epoch) and report its accuracy')
+    parser.add_argument('--reward-epochs', type=int, default=None, help='with --fit-reward: epochs of the reward fit (default: 30)')
+    parser.add_argument('--reward-batch-size', type=int, default=None,
+                        help='with --fit-reward: minibatch size of the reward fit (default: 32)')
+    parser.add_argument('--reward-lr', type=float, default=None, help='with --fit-reward: learning rate of the reward fit (default: 0.005)')
     return parser
 
 
@@ -131,7 +160,8 @@ def report(result):
 
 def run_fit(args):
     """--fit: the head fitted on the training episodes, the k-step error on the validation and on the training transitions."""
-    states, actions, _, episode_starts = prepare(args)
+    states, actions, rewards, episode_starts = prepare(args)
+    fit_reward = getattr(args, "fit_reward", False)
     from srlz import dynfit
     from srlz.deploy import LatentDynamics
     states = np.asarray(states, np.float32)
@@ -143,8 +173,20 @@ def run_fit(args):
     dyn = LatentDynamics.from_recording(states, actions, episode_starts, n_actions=n_actions, ridge=args.ridge, starts=train,
                                         max_horizon=max(32, args.horizon))
     fit = dyn.fit
-    on_val = dyn.horizon_error(states, actions, episode_starts, args.horizon, starts=val)
-    on_train = dyn.horizon_error(states, actions, episode_starts, args.horizon, starts=train)
+    asked = None
+    if fit_reward:
+        asked = rewards
+        from srlz import headfit
+        # the validation episodes stay out of the fit altogether: the kept epoch is picked on a fifth of the TRAINING episodes
+        fit_side, select_side = headfit.split_starts(train, episode_starts, 0.2, args.seed)
+        rfit = dyn.refit_reward(states, rewards, episode_starts, starts=fit_side, val_starts=select_side, seed=args.seed,
+                                epochs=args.reward_epochs, batch_size=args.reward_batch_size, lr=args.reward_lr)
+        print("Reward head fitted on {} transitions: route {}, epoch {} of {} kept on {} further training transitions "
+              "(loss {:.6g}, accuracy {:.4f})".format(
+                  rfit.count, rfit.route, rfit.best_epoch + 1, rfit.epochs, rfit.val_count, rfit.history[rfit.best_epoch]["val_loss"],
+                  rfit.history[rfit.best_epoch]["val_accuracy"]))
+    on_val = dyn.horizon_error(states, actions, episode_starts, args.horizon, rewards=asked, starts=val)
+    on_train = dyn.horizon_error(states, actions, episode_starts, args.horizon, rewards=asked, starts=train)
     print("Open-loop error of the fitted forward head over {} steps on {} validation transitions ({} fitted, fit route {}, route {})"
           .format(args.horizon, len(val), fit.count, fit.route, dyn.route))
     for line in report(on_val):
@@ -153,6 +195,8 @@ def run_fit(args):
     out["train"] = on_train.as_dict()
     out["fit"] = {"ridge": fit.ridge, "count": fit.count, "val_fraction": args.val_fraction, "seed": args.seed, "route": fit.route,
                   "state_dim": fit.state_dim, "n_actions": fit.n_actions}
+    if fit_reward:
+        out["reward_fit"] = rfit.as_dict()
     log_folder = args.log_folder if args.log_folder.endswith("/") else args.log_folder + "/"
     with open(os.path.join(log_folder, OUTPUT_FIT), "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)

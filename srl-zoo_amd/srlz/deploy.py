@@ -647,6 +647,13 @@ def reconstruct(encoder, decoder, frames):
 #     dyn = LatentDynamics.from_recording(states, actions, episode_starts, n_actions=None, ridge=1e-6, starts=None)
 #     fit = dyn.refit_forward(states, actions, episode_starts, ridge=1e-6, starts=None)     # a model's own head, in place
 #     fit.weight, fit.bias, fit.weight64, fit.bias64, fit.count, fit.gram, fit.cross, fit.route
+#
+# A reward head without training.  The reward head is a three-layer classifier: its optimum has no closed form, so it is trained on
+# the recording with Adam, one launch per epoch (srlz/headfit.py, csrc/headfit.hip).  With it a recording's dynamics
+# roll, plan and search by reward, without a goal:
+#     dyn = LatentDynamics.from_recording(states, actions, episode_starts, rewards=rewards, reward_fit=dict(epochs=30))
+#     rfit = dyn.refit_reward(states, rewards, episode_starts, epochs=30, batch_size=32, lr=0.005, seed=0)   # a model's own head, in place
+#     rfit.state_dict, rfit.history, rfit.best_epoch, rfit.count, rfit.val_count, rfit.route
 # =============================================================================================================
 ROUTE_ROLLOUT = "rollout"
 HEADS = ("forward", "inverse", "reward")
@@ -1212,6 +1219,7 @@ class LatentDynamics(object):
         self._search_bufs = {}  # the tree search's device buffers: made by the first search call
         self._forced_model = route is not None
         self.fit = None  # the ForwardFit of the last refit_forward / from_recording
+        self.reward_fit = None  # the RewardFit of the last refit_reward / from_recording(rewards=)
         self.device = next(self.owner.forward_net.parameters()).device
         if self.device.type != "cuda":
             raise C.SrlzError("LatentDynamics: the model must live on the GPU (there is no CPU path)")
@@ -1247,12 +1255,16 @@ class LatentDynamics(object):
         return self.last_route or self._route
 
     @classmethod
-    def from_recording(cls, states, actions, episode_starts, n_actions=None, ridge=1e-6, starts=None, max_rows=8192, max_horizon=32):
+    def from_recording(cls, states, actions, episode_starts, n_actions=None, ridge=1e-6, starts=None, max_rows=8192, max_horizon=32,
+                       rewards=None, reward_fit=None):
         """Dynamics for a representation that has no network behind it (PCA, supervised or ground-truth states, a model trained
         without the forward loss): the three heads alone (srlz.dynfit.heads_only_modules, losses = ["forward"], no encoder), the
         forward head fitted to the recording in closed form (srlz.dynfit.fit_forward; the arguments are its own).  The route is the
-        one a trained model of these dimensions takes.  The reward and inverse heads are untrained and stay unused: goal= planning
-        works on the distance term alone.  The fit is kept as .fit."""
+        one a trained model of these dimensions takes.  Without `rewards` the reward head is untrained and stays unused, and goal=
+        planning works on the distance term alone; with `rewards` [N] the forward fit is followed by refit_reward on the same
+        transitions (reward_fit: a dict of srlz.headfit.fit_reward keyword arguments; `starts`, when given, are its training
+        transitions too, and its validation transitions are then the recording's other transitions unless reward_fit names them), "reward" joins the heads and plan, search and rollout work without a goal.  The inverse head is untrained
+        and stays unused either way.  The fits are kept as .fit and .reward_fit."""
         from . import dynfit
         from models.learner import _requireGpu
         _requireGpu(True)
@@ -1261,6 +1273,20 @@ class LatentDynamics(object):
         model.eval()
         dyn = cls(model, max_rows=max_rows, max_horizon=max_horizon)
         dyn._install_fit(fit)
+        if rewards is not None:
+            kw = dict(reward_fit or {})
+            if starts is not None and "starts" not in kw:
+                kw["starts"] = starts
+                if "val_starts" not in kw:  # the recording's other transitions: never the ones the head is trained on
+                    from . import dynfit
+                    rest = np.setdiff1d(dynfit.transitions(episode_starts), np.asarray(dynfit._host(starts)).reshape(-1))
+                    if rest.size < 1:
+                        raise ValueError("starts lists every transition of the recording: the reward fit has none left to pick its "
+                                         "epoch on (give reward_fit=dict(val_starts=...), or fewer starts)")
+                    kw["val_starts"] = rest.astype(np.int32)
+            dyn.refit_reward(states, rewards, episode_starts, **kw)
+        elif reward_fit is not None:
+            raise ValueError("reward_fit configures the fit of the reward head: it needs rewards=")
         return dyn
 
     def _install_fit(self, fit):
@@ -1291,8 +1317,35 @@ class LatentDynamics(object):
         self._install_fit(fit)
         return fit
 
+    def refit_reward(self, states, rewards, episode_starts, **fit_kwargs):
+        """Train the reward head on a recorded sequence (srlz.headfit.fit_reward; hidden = the head's own H, the other keyword
+        arguments are fit_reward's) and copy the kept epoch's parameters into owner.reward_net IN PLACE, under no_grad -> the
+        RewardFit, kept as .reward_fit.  "reward" joins self.heads, whatever the model's losses trained.  Nothing has to be
+        refreshed, for refit_forward's reason: every launch takes the head's weights by address at every call.  ValueError when the
+        recording's state_dim is not the head's, when reward_net is not the reference's three-layer head with two classes
+        (dynamics_dims gives H = 0), when hidden= names another width; fit_reward's ValueErrors as they are."""
+        from . import headfit
+        if not isinstance(states, (np.ndarray, torch.Tensor)) or len(states.shape) != 2 or states.shape[1] != self.state_dim:
+            raise ValueError("the recording's states of shape %s do not match the head's state_dim = %d"
+                             % (tuple(getattr(states, "shape", ())), self.state_dim))
+        if self._h < 1 or self._nr != 2:
+            raise ValueError("refit_reward needs the reference's reward head Linear(2S,H)-ReLU-Linear(H,H)-ReLU-Linear(H,2) with "
+                             "biases; this model's reward_net is something else")
+        if int(fit_kwargs.setdefault("hidden", self._h)) != self._h:
+            raise ValueError("hidden=%r is not the head's own width %d" % (fit_kwargs["hidden"], self._h))
+        fit = headfit.fit_reward(states, rewards, episode_starts, **fit_kwargs)
+        rn = self.owner.reward_net
+        with torch.no_grad():
+            for key, value in fit.state_dict.items():
+                layer, name = key.split(".")
+                getattr(rn[int(layer)], name).copy_(value)
+        if "reward" not in self.heads:
+            self.heads = tuple(h for h in HEADS if h in self.heads or h == "reward")
+        self.reward_fit = fit
+        return fit
+
     def _need(self, head):
-        if head in self.heads:  # (refit_forward adds "forward" to the heads the losses trained)
+        if head in self.heads:  # (refit_forward / refit_reward add their head to the heads the losses trained)
             return
         check_head(self.owner, head, self.untrained_ok)
 

@@ -9,7 +9,9 @@ MSE.  Over a recorded dataset the minimiser needs no SGD: with z = [s | onehot(a
 of a (S + A + 1)-square system.  The only work that grows with the dataset is G = sum z zᵀ and C = sum z yᵀ over the transitions:
 route "gram" is csrc/dynfit.hip (fp64 MFMA, nothing materialised, reproducible bits, G exactly symmetric), route "torch" builds Z and
 Y in fp64 on the device and takes two matmuls — for shapes srlz_dynfit_supported refuses, or when forced for a measurement.  The
-small system is solved in fp64 numpy on the host.  DESIGN.md §3.20.
+small system is solved in fp64 numpy on the host.  DESIGN.md §3.20.  The reward head of the same representations has no closed
+form: srlz/headfit.py trains it on the recording (LatentDynamics.refit_reward, from_recording(rewards=)); the split by episodes and
+the heads-only module are shared with it.
 
 transitions, split_episodes and solve_forward_head are pure host functions: no GPU is asked for.
 """

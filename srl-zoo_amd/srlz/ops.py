@@ -1990,34 +1990,34 @@ def reward_probe_stats(device=None):
     return torch.zeros(1, dtype=torch.float64, device=device), torch.zeros(5, dtype=torch.int64, device=device)
 
 
-def _reward_probe_buffer(t, name, dtype, numel, data, exact=False):
+def _reward_probe_buffer(t, name, dtype, numel, data, exact=False, who="reward_probe"):
     if not torch.is_tensor(t) or t.device != data.states.device:
-        raise C.SrlzError("reward_probe: %s must be a tensor on %s: the srl-zoo_amd hot path has no CPU fallback" % (name, data.states.device))
+        raise C.SrlzError("%s: %s must be a tensor on %s: the srl-zoo_amd hot path has no CPU fallback" % (who, name, data.states.device))
     if t.dtype != dtype:
-        raise ValueError("reward_probe: %s must be %s (got %s)" % (name, dtype, t.dtype))
+        raise ValueError("%s: %s must be %s (got %s)" % (who, name, dtype, t.dtype))
     if not t.is_contiguous():
-        raise ValueError("reward_probe: %s must be contiguous" % name)
+        raise ValueError("%s: %s must be contiguous" % (who, name))
     if (t.numel() != numel) if exact else (t.numel() < numel):
-        raise ValueError("reward_probe: %s holds %d elements, needs %s%d (S = %d)" % (name, t.numel(), "" if exact else "at least ",
-                                                                                      numel, data.s))
+        raise ValueError("%s: %s holds %d elements, needs %s%d (S = %d)" % (who, name, t.numel(), "" if exact else "at least ",
+                                                                          numel, data.s))
     return t
 
 
-def _reward_probe_table(data, idx):
+def _reward_probe_table(data, idx, who="reward_probe"):
     """The minibatch table: int32 [n, B] on the HOST (the launcher checks every entry there), C-contiguous -> (host, device)."""
     import numpy as np
     if not isinstance(data, RewardProbeData):
-        raise ValueError("reward_probe: data must come from reward_probe_data()")
+        raise ValueError("%s: data must come from reward_probe_data()" % who)
     if isinstance(idx, np.ndarray):
         idx = torch.from_numpy(idx)
     if not torch.is_tensor(idx) or idx.device.type != "cpu":
-        raise ValueError("reward_probe: idx must be a host tensor (it is checked on the host, then uploaded)")
+        raise ValueError("%s: idx must be a host tensor (it is checked on the host, then uploaded)" % who)
     if idx.dtype != torch.int32:
-        raise ValueError("reward_probe: idx must be int32 (got %s)" % idx.dtype)
+        raise ValueError("%s: idx must be int32 (got %s)" % (who, idx.dtype))
     if idx.dim() != 2 or idx.shape[0] < 1 or idx.shape[1] < 1:
-        raise ValueError("reward_probe: idx must be a non-empty [minibatches, B] table (got shape %s)" % (tuple(idx.shape),))
+        raise ValueError("%s: idx must be a non-empty [minibatches, B] table (got shape %s)" % (who, tuple(idx.shape)))
     if not idx.is_contiguous():
-        raise ValueError("reward_probe: idx must be contiguous")
+        raise ValueError("%s: idx must be contiguous" % who)
     return idx, idx.to(data.states.device)
 
 
@@ -2630,3 +2630,95 @@ def dynfit_gram(states, actions, starts, n_actions, gram=None, cross=None, works
     C.dynfit_gram(ptr(states), ptr(actions), ptr(d_starts), ctypes.c_void_p(starts.data_ptr()), n, m, s, a, ptr(gram), ptr(cross),
                   ptr(workspace), workspace.numel(), stream())
     return gram, cross
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# The reward head on a recorded sequence (csrc/headfit.hip; include/srlz.h states the layout, every sum's order and the limits):
+# an epoch of Adam steps in one launch, a validation phase in one more.  The (states, labels) pair is reward_probe_data's; the
+# argument checks and error types are those of reward_probe_fit / reward_probe_eval.
+# ----------------------------------------------------------------------------------------------------------------
+def headfit_supported(s, h):
+    return bool(C.headfit_supported(int(s), int(h)))
+
+
+def headfit_n_params(s, h):
+    """Linear(2S, H), Linear(H, H), Linear(H, 2) with their biases, flat in state_dict order (0 for S < 1 or H < 1)."""
+    return int(C.headfit_n_params(int(s), int(h)))
+
+
+def headfit_chunk_rows(s, h):
+    """Rows of a minibatch that srlz_headfit_fit processes at a time (a function of S and H alone; 0 for a refused shape)."""
+    return int(C.headfit_chunk_rows(int(s), int(h)))
+
+
+class HeadfitTable(object):
+    """A minibatch table int32 [n, B] on the host and its device copy (headfit_table): built once, passed to many launches."""
+
+    def __init__(self, host, device):
+        self.host, self.device = host, device
+
+
+def headfit_table(data, idx):
+    """int32 [n, B] host table -> HeadfitTable, uploaded once (the launchers check the host copy at every call)."""
+    if isinstance(idx, HeadfitTable):
+        if not isinstance(data, RewardProbeData) or idx.device.device != data.states.device:
+            raise ValueError("headfit: the table was uploaded for other data")
+        return idx
+    return HeadfitTable(*_reward_probe_table(data, idx, who="headfit"))
+
+
+def _headfit_shape(data, hidden):
+    if not isinstance(data, RewardProbeData):
+        raise ValueError("headfit: data must come from reward_probe_data()")
+    h = int(hidden)
+    if not headfit_supported(data.s, h):
+        raise ValueError("headfit: state_dim %d with %d hidden units is outside srlz_headfit_supported" % (data.s, h))
+    return h
+
+
+def headfit_fit(data, idx, hidden, params, m, v, t0, lr, running_loss, counts, step_loss=None, last_grad=None, betas=(0.9, 0.999),
+                eps=1e-8):
+    """idx.shape[0] consecutive Adam steps of the reward head (Linear(2S,H)-ReLU-Linear(H,H)-ReLU-Linear(H,2), cross-entropy) in
+    ONE launch of srlz_headfit_fit: minibatch s is the rows [states[i] ; states[i + 1]] for i in idx[s], labelled labels[i].  No
+    autograd: the kernel owns the backward.  data: reward_probe_data(states, labels); idx: an int32 [n, B] host table or a
+    headfit_table; params / m / v: float32 [headfit_n_params(S, H)] on the device in state_dict order, updated in place; t0: the
+    Adam steps already taken; running_loss float64 [1] and counts int64 [5] are added to (reward_probe_stats); step_loss: float64
+    [>= steps] for the mean loss of every step, or None; last_grad: float32 [n_params] for the last step's gradient, or None."""
+    h = _headfit_shape(data, hidden)
+    tb = headfit_table(data, idx)
+    n_steps, b = int(tb.host.shape[0]), int(tb.host.shape[1])
+    n_par = headfit_n_params(data.s, h)
+    for t, name in ((params, "params"), (m, "m"), (v, "v")):
+        _reward_probe_buffer(t, name, torch.float32, n_par, data, exact=True, who="headfit")
+    _reward_probe_buffer(running_loss, "running_loss", torch.float64, 1, data, who="headfit")
+    _reward_probe_buffer(counts, "counts", torch.int64, 5, data, who="headfit")
+    if step_loss is not None:
+        _reward_probe_buffer(step_loss, "step_loss", torch.float64, n_steps, data, who="headfit")
+    if last_grad is not None:
+        _reward_probe_buffer(last_grad, "last_grad", torch.float32, n_par, data, exact=True, who="headfit")
+    C.headfit_fit(ptr(data.states), ptr(data.labels), data.n, data.s, h, ptr(tb.device), ctypes.c_void_p(tb.host.data_ptr()), n_steps, b,
+                  ptr(params), ptr(m), ptr(v), int(t0), float(lr), float(betas[0]), float(betas[1]), float(eps), ptr(running_loss),
+                  ptr(counts), ptr(step_loss), ptr(last_grad), stream())
+
+
+def headfit_eval(data, idx, hidden, params, running_loss, counts, workspace=None):
+    """The forward, loss (float64 per row) and counts of idx.shape[0] minibatches in ONE launch of srlz_headfit_eval; params are only
+    read, running_loss and counts are added to.  workspace: a contiguous uint8 device tensor of at least
+    srlz_headfit_eval_workspace(n, B) bytes, made here when None."""
+    h = _headfit_shape(data, hidden)
+    tb = headfit_table(data, idx)
+    n_batches, b = int(tb.host.shape[0]), int(tb.host.shape[1])
+    _reward_probe_buffer(params, "params", torch.float32, headfit_n_params(data.s, h), data, exact=True, who="headfit")
+    _reward_probe_buffer(running_loss, "running_loss", torch.float64, 1, data, who="headfit")
+    _reward_probe_buffer(counts, "counts", torch.int64, 5, data, who="headfit")
+    device = data.states.device
+    ticket = _REWARD_PROBE_TICKET.get(device.index)
+    if ticket is None:
+        ticket = _REWARD_PROBE_TICKET[device.index] = torch.zeros(1, dtype=torch.int32, device=device)
+    nbytes = int(C.headfit_eval_workspace(n_batches, b))
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=device)
+    else:
+        _reward_probe_buffer(workspace, "workspace", torch.uint8, nbytes, data, who="headfit")
+    C.headfit_eval(ptr(data.states), ptr(data.labels), data.n, data.s, h, ptr(tb.device), ctypes.c_void_p(tb.host.data_ptr()), n_batches,
+                   b, ptr(params), ptr(running_loss), ptr(counts), ptr(workspace), workspace.numel(), ptr(ticket), stream())
