@@ -1232,6 +1232,66 @@ int srlz_headfit_eval(const float* states /*[N,S]*/, const int* labels /*[N]*/, 
                       long long* counts /*[5]*/, void* ws, size_t ws_bytes, unsigned* ticket, srlz_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The inverse head fitted on a recording (csrc/invfit.hip; srlz/invfit.py, LatentDynamics.refit_inverse / action_accuracy,
+ * evaluation/predict_forward.py --fit --fit-inverse).  Replaces the inverse part of the learner's minibatch loop,
+ *   actions_pred = model.inverseModel(states, next_states)      models/forward_inverse.py inverseModel (:62-70): the head
+ *                                                               nn.Linear(2S, A) on th.cat((state, next_state), dim=1)
+ *   inverseModelLoss(...) -> nn.CrossEntropyLoss                losses/losses.py:117-129
+ *   loss.backward(); optimizer.step()                           the learner's Adam loop (models/learner.py)
+ * by ONE launch per training epoch (srlz_invfit_fit) and ONE per validation phase (srlz_invfit_eval): multinomial logistic
+ * regression, z = W [s_i ; s_{i+1}] + b.  The shape of srlz_headfit_*, whose entry points and bits are unchanged.
+ *   states [N, S] fp32 and labels [N] int32 (the action of frame i) stay on the device.  idx / idx_host: as srlz_headfit_fit takes
+ *   them (every entry checked on the host against [0, N - 2], the device copy clamped as it is read).  Row b of minibatch s is the
+ *   2S floats at states + idx[s][b] * S; its label is labels[idx[s][b]].  A label outside [0, A) indexes nothing: its row adds
+ *   zero to the loss and to the gradient (the mean still divides by B) and is counted in `bad`.
+ *   params / m / v / last_grad: srlz_invfit_n_params(S, A) = 2S*A + A floats each in state_dict order (inverse_net.weight [A, 2S],
+ *   inverse_net.bias [A]).  running_loss [1] fp64 and counts [3 + 2A] int64 are ADDED TO; counts = rows, correct, bad, then
+ *   support[A] (rows labelled a) and hits[A] (of which predicted a): rows = sum(support) + bad, correct = sum(hits), and
+ *   hits[a] / support[a] is the recall of action a.  An argmax tie goes to the lowest class, as th.max does.
+ * fit: n_steps consecutive Adam steps (the arithmetic of srlz_adam_step) in one launch of one persistent workgroup of 256 threads.
+ *   Parameters and gradient stay in LDS from the first step to the last; the Adam moments m and v stay in GLOBAL memory in
+ *   state_dict order, read and written once per step (two more copies in LDS would halve the envelope).  Step s uses the bias
+ *   corrections of t = t0 + s + 1.  Forward in fp32, cross-entropy as the mean over B in log-sum-exp form; no gradient into the
+ *   states.  Rows are processed in chunks of srlz_invfit_chunk_rows(S, A).  Order of every sum, a function of (S, A, B) alone:
+ *   logits — 16 lanes per row, lane kk adds k = kk, kk + 16, .. ascending, then a butterfly over the 16 lanes (offsets 8, 4, 2, 1),
+ *   then + bias; softmax — one thread per row, the maximum and e_j = exp(z_j - max) over j ascending, the e_j beside the label's
+ *   added over j ascending and the label's added last; loss = log1p(others) where the label holds the maximum, else log(sum) -
+ *   (z_label - max); dz_j = e_j / sum / B, the label's -(others) / sum / B; every parameter's gradient — one thread per element,
+ *   rows in row order, chunk after chunk; the loss — per chunk, lane l of one wave adds rows l, l + 64 in fp64, then a butterfly,
+ *   chunks in order.  running_loss += (sum of row losses / B) * B per step in fp64; step_loss (may be NULL) receives the n_steps
+ *   mean losses; last_grad (may be NULL) the gradient of the LAST step.  No float atomics (support and hits are integer atomics
+ *   in LDS), plain vector stores.  Two calls leave identical bits; n steps in one call and n calls of one step leave identical
+ *   bits in params, m, v, running_loss, counts and step_loss.
+ * eval: the same logits over n_batches * B independent rows, 64 per workgroup (16 at a time), the row loss in fp64 as
+ *   max + log(sum_j exp(z_j - max)) - z_label, j ascending; per-workgroup sums (lane l = row l, a butterfly) go to ws
+ *   (srlz_invfit_eval_workspace(n_batches, B) bytes) and are added in workgroup order by the workgroup that finishes last
+ *   (`ticket`: one zeroed unsigned the kernel leaves zeroed; no spinning, no grid barrier); counts by integer atomics.  params
+ *   are only read.
+ * Limits: the LDS budget and nothing else.  With K = 2S, AP = A rounded up to a multiple of 4, APAD = AP | 4, the LDS image of the
+ *   parameters holds (K + 1) * APAD floats (row k < K is W[:, k], row K the bias; pads zero and never written back), the gradient
+ *   as many, the per-action counters 2 * APAD, Adam's table 512, and a row of a chunk costs (K | 1) + APAD + 3 floats (the row,
+ *   its z / dz, loss, flag, label), within the 160 KB srlz_headfit_fit uses:
+ *   srlz_invfit_chunk_rows(S, A) = min(128, floor((40444 - 2 * (K + 2) * APAD) / ((K | 1) + APAD + 3))), and 0 where that is below
+ *   16, S < 1 or A < 2;  srlz_invfit_supported(S, A) = srlz_invfit_chunk_rows(S, A) > 0.
+ *   That accepts S = 200 with A = 6 (chunks of 74 rows), S <= 501 up to A = 8, S <= 356 up to A = 16, S <= 225 up to
+ *   A = 32, S <= 839 up to A = 4, and at S = 1 up to A = 1676.
+ * Refused before anything is enqueued, nothing written: an unsupported (S, A), N < 2, n < 1, B < 1, N * S >= 2^31, n * B >= 2^31,
+ *   t0 < 0, an entry of idx_host outside [0, N - 2]: SRLZ_ERR_BAD_DESC; a missing pointer SRLZ_ERR_NULL; ws_bytes below
+ *   srlz_invfit_eval_workspace: SRLZ_ERR_WORKSPACE.  srlz_invfit_eval_workspace returns 0 for n_batches < 1, B < 1 or 2^31 rows.
+ * ------------------------------------------------------------------------------------------------------------ */
+int srlz_invfit_supported(int S, int A);
+long long srlz_invfit_n_params(int S, int A); /* 2S*A + A; 0 for S < 1 or A < 2 */
+int srlz_invfit_chunk_rows(int S, int A);     /* rows of a chunk; 0 for a shape the launchers reject */
+int srlz_invfit_fit(const float* states /*[N,S]*/, const int* labels /*[N]*/, int N, int S, int A, const int* idx /*[n_steps,B]*/,
+                    const int* idx_host /*[n_steps,B]*/, int n_steps, int B, float* params, float* m, float* v, int t0, double lr,
+                    double beta1, double beta2, double eps, double* running_loss /*[1]*/, long long* counts /*[3 + 2A]*/,
+                    double* step_loss /*[n_steps] or NULL*/, float* last_grad /*[P] or NULL*/, srlz_stream_t stream);
+size_t srlz_invfit_eval_workspace(int n_batches, int B);
+int srlz_invfit_eval(const float* states /*[N,S]*/, const int* labels /*[N]*/, int N, int S, int A, const int* idx /*[n_batches,B]*/,
+                     const int* idx_host /*[n_batches,B]*/, int n_batches, int B, const float* params, double* running_loss /*[1]*/,
+                     long long* counts /*[3 + 2A]*/, void* ws, size_t ws_bytes, unsigned* ticket, srlz_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Debug / calibration hooks (not on the product path).
  * ------------------------------------------------------------------------------------------------------------ */
 /* Host-only: dump the virtual-grid program of a 64->64 convolution (tests interpret it on the CPU).

@@ -35,6 +35,17 @@ gain reward_accuracy / majority_accuracy, and the JSON one object "reward_fit": 
 best_epoch, count, val_count (the two shares of the training transitions) and the per-epoch train_loss, val_loss, train_accuracy, val_accuracy.  "fit" keeps its keys.
 --fit-reward without --fit, and the --reward-* flags without --fit-reward, are an error.
 
+    python -m evaluation.predict_forward --log-folder logs/<dataset>/<experiment>/ --fit --fit-inverse
+                                         [--inverse-epochs 30] [--inverse-batch-size 32] [--inverse-lr 0.005]
+
+With --fit --fit-inverse the inverse head Linear(2S, A) is fitted as well (srlz.invfit, DESIGN.md §3.22: Adam, one launch per epoch,
+the same two shares of the training episodes) and asked for the recorded action of every validation transition: can the action be
+read off (s, s') in this space, on held-out episodes?  One line is printed and the JSON gains one object "inverse_fit": accuracy,
+majority_accuracy, recall (per action, null for an action the validation episodes never took), count (all four on the validation
+transitions), best_epoch, route, and epochs, batch_size, lr, seed, fit_count, select_count.  Without the flag the file and the
+printed lines are what they are without it.  --fit-inverse without --fit, and the --inverse-* flags without --fit-inverse, are an
+error.
+
 There is no reference counterpart: the reference has no metric for its dynamics heads.  --no-cuda, or a machine without a GPU,
 raises: this build has no CPU fallback.
 """
@@ -55,6 +66,9 @@ OUTPUT_FIT = "forward_horizon_fit.json"
 FIT_KEYS = ("ridge", "count", "val_fraction", "seed", "route", "state_dim", "n_actions")
 FIT_DEFAULTS = (("ridge", 1e-6), ("val_fraction", 0.2), ("seed", 0))  # what --fit uses for a flag that was not given
 REWARD_DEFAULTS = (("reward_epochs", 30), ("reward_batch_size", 32), ("reward_lr", 0.005))  # train.py's own, with --fit-reward
+INVERSE_DEFAULTS = (("inverse_epochs", 30), ("inverse_batch_size", 32), ("inverse_lr", 0.005))  # the same, with --fit-inverse
+INVERSE_KEYS = ("accuracy", "majority_accuracy", "recall", "count", "best_epoch", "route", "epochs", "batch_size", "lr", "seed",
+                "fit_count", "select_count")
 KEYS = ("horizon", "count", "mse", "baseline_mse", "ratio", "reward_accuracy", "majority_accuracy")
 
 
@@ -69,10 +83,16 @@ class _Parser(argparse.ArgumentParser):
                                            ("--reward-lr", ns.reward_lr is not None)) if on]
             if given:
                 self.error("{} only with --fit-reward".format(", ".join(given)))
+        if not ns.fit_inverse:
+            given = [flag for flag, on in (("--inverse-epochs", ns.inverse_epochs is not None),
+                                           ("--inverse-batch-size", ns.inverse_batch_size is not None),
+                                           ("--inverse-lr", ns.inverse_lr is not None)) if on]
+            if given:
+                self.error("{} only with --fit-inverse".format(", ".join(given)))
         if not ns.fit:
             given = [flag for flag, on in (("--ground-truth", ns.ground_truth), ("--ridge", ns.ridge is not None),
                                            ("--val-fraction", ns.val_fraction is not None), ("--seed", ns.seed is not None),
-                                           ("--fit-reward", ns.fit_reward)) if on]
+                                           ("--fit-reward", ns.fit_reward), ("--fit-inverse", ns.fit_inverse)) if on]
             if given:
                 self.error("{} only with --fit".format(", ".join(given)))
             return ns
@@ -83,6 +103,10 @@ class _Parser(argparse.ArgumentParser):
                 setattr(ns, name, default)
         if ns.fit_reward:
             for name, default in REWARD_DEFAULTS:
+                if getattr(ns, name) is None:
+                    setattr(ns, name, default)
+        if ns.fit_inverse:
+            for name, default in INVERSE_DEFAULTS:
                 if getattr(ns, name) is None:
                     setattr(ns, name, default)
         return ns
@@ -112,6 +136,12 @@ def build_parser():
     parser.add_argument('--reward-batch-size', type=int, default=None,
                         help='with --fit-reward: minibatch size of the reward fit (default: 32)')
     parser.add_argument('--reward-lr', type=float, default=None, help='with --fit-reward: learning rate of the reward fit (default: 0.005)')
+    parser.add_argument('--fit-inverse', action='store_true', default=False,
+                        help='with --fit: fit the inverse head too (Adam, one launch per epoch) and report its held-out accuracy')
+    parser.add_argument('--inverse-epochs', type=int, default=None, help='with --fit-inverse: epochs of the inverse fit (default: 30)')
+    parser.add_argument('--inverse-batch-size', type=int, default=None,
+                        help='with --fit-inverse: minibatch size of the inverse fit (default: 32)')
+    parser.add_argument('--inverse-lr', type=float, default=None, help='with --fit-inverse: learning rate of the inverse fit (default: 0.005)')
     return parser
 
 
@@ -185,6 +215,19 @@ def run_fit(args):
               "(loss {:.6g}, accuracy {:.4f})".format(
                   rfit.count, rfit.route, rfit.best_epoch + 1, rfit.epochs, rfit.val_count, rfit.history[rfit.best_epoch]["val_loss"],
                   rfit.history[rfit.best_epoch]["val_accuracy"]))
+    if getattr(args, "fit_inverse", False):
+        from srlz import headfit
+        fit_side, select_side = headfit.split_starts(train, episode_starts, 0.2, args.seed)  # as the reward fit: validation stays out
+        ifit = dyn.refit_inverse(states, actions, episode_starts, starts=fit_side, val_starts=select_side, seed=args.seed,
+                                 epochs=args.inverse_epochs, batch_size=args.inverse_batch_size, lr=args.inverse_lr)
+        acc = dyn.action_accuracy(states, actions, episode_starts, starts=val)
+        inverse = {"accuracy": acc.accuracy, "majority_accuracy": acc.majority_accuracy, "recall": acc.recall, "count": acc.count,
+                   "best_epoch": ifit.best_epoch, "route": ifit.route, "epochs": ifit.epochs, "batch_size": ifit.batch_size,
+                   "lr": ifit.lr, "seed": ifit.seed, "fit_count": ifit.count, "select_count": ifit.val_count}
+        print("Inverse head fitted on {} transitions: route {}, epoch {} of {} kept on {} further training transitions; on {} "
+              "validation transitions action acc {:.4f} (majority {:.4f}), recall {}".format(
+                  ifit.count, ifit.route, ifit.best_epoch + 1, ifit.epochs, ifit.val_count, acc.count, acc.accuracy,
+                  acc.majority_accuracy, " ".join("-" if r is None else "{:.2f}".format(r) for r in acc.recall)))
     on_val = dyn.horizon_error(states, actions, episode_starts, args.horizon, rewards=asked, starts=val)
     on_train = dyn.horizon_error(states, actions, episode_starts, args.horizon, rewards=asked, starts=train)
     print("Open-loop error of the fitted forward head over {} steps on {} validation transitions ({} fitted, fit route {}, route {})"
@@ -197,6 +240,8 @@ def run_fit(args):
                   "state_dim": fit.state_dim, "n_actions": fit.n_actions}
     if fit_reward:
         out["reward_fit"] = rfit.as_dict()
+    if getattr(args, "fit_inverse", False):
+        out["inverse_fit"] = inverse
     log_folder = args.log_folder if args.log_folder.endswith("/") else args.log_folder + "/"
     with open(os.path.join(log_folder, OUTPUT_FIT), "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)

@@ -305,6 +305,13 @@ _PROTOS = {
                                  P, P, P, P, P]),
     "srlz_headfit_eval_workspace": (c_size_t, [c_int, c_int]),
     "srlz_headfit_eval": (c_int, [P, P, c_int, c_int, c_int, P, P, c_int, c_int, P, P, P, P, c_size_t, P, P]),
+    "srlz_invfit_supported": (c_int, [c_int, c_int]),
+    "srlz_invfit_n_params": (c_longlong, [c_int, c_int]),
+    "srlz_invfit_chunk_rows": (c_int, [c_int, c_int]),
+    "srlz_invfit_fit": (c_int, [P, P, c_int, c_int, c_int, P, P, c_int, c_int, P, P, P, c_int, c_double, c_double, c_double, c_double,
+                                P, P, P, P, P]),
+    "srlz_invfit_eval_workspace": (c_size_t, [c_int, c_int]),
+    "srlz_invfit_eval": (c_int, [P, P, c_int, c_int, c_int, P, P, c_int, c_int, P, P, P, P, c_size_t, P, P]),
 }
 
 # entry points whose int return value is data, not a status
@@ -320,7 +327,8 @@ _NOT_STATUS = {"srlz_version", "srlz_device_cus", "srlz_conv64_fwd_tiles", "srlz
                "srlz_conv1_buffer_staging_supported", "srlz_infer_dec_supported", "srlz_infer_dec_tile", "srlz_rollout_supported",
                "srlz_rollout_tile", "srlz_plan_supported", "srlz_rollout_goal_supported", "srlz_plan_goal_supported",
                "srlz_horizon_supported", "srlz_beam_supported", "srlz_beam_leaves", "srlz_dynfit_supported",
-               "srlz_dynfit_chunk_rows", "srlz_headfit_supported", "srlz_headfit_chunk_rows"}
+               "srlz_dynfit_chunk_rows", "srlz_headfit_supported", "srlz_headfit_chunk_rows", "srlz_invfit_supported",
+               "srlz_invfit_chunk_rows"}
 
 EXPORTED = sorted(_PROTOS.keys())
 

@@ -654,6 +654,15 @@ def reconstruct(encoder, decoder, frames):
 #     dyn = LatentDynamics.from_recording(states, actions, episode_starts, rewards=rewards, reward_fit=dict(epochs=30))
 #     rfit = dyn.refit_reward(states, rewards, episode_starts, epochs=30, batch_size=32, lr=0.005, seed=0)   # a model's own head, in place
 #     rfit.state_dict, rfit.history, rfit.best_epoch, rfit.count, rfit.val_count, rfit.route
+#
+# An inverse head without training.  "Can the action be read off (state, next state)?" — this zoo's default loss — has no closed
+# form either: Linear(2S, A) under a cross-entropy, trained on the recording with Adam, one launch per epoch (srlz/invfit.py,
+# csrc/invfit.hip).  With it action_logits works, and action_accuracy says which actions the representation keeps:
+#     dyn = LatentDynamics.from_recording(states, actions, episode_starts, inverse_fit=dict(epochs=30))
+#     ifit = dyn.refit_inverse(states, actions, episode_starts, epochs=30, batch_size=32, lr=0.005, seed=0)  # a model's own head, in place
+#     ifit.state_dict, ifit.history, ifit.best_epoch, ifit.count, ifit.val_count, ifit.route
+#     acc = dyn.action_accuracy(states, actions, episode_starts, starts=None)     # one srlz_invfit_eval launch for a linear head
+#     acc.accuracy, acc.majority_accuracy, acc.recall, acc.support, acc.hits, acc.loss, acc.count, acc.route
 # =============================================================================================================
 ROUTE_ROLLOUT = "rollout"
 HEADS = ("forward", "inverse", "reward")
@@ -666,6 +675,19 @@ class Rollout(object):
     def __init__(self, final_states, returns=None, trajectory=None, reward_logits=None, best=None, goal_dist=None):
         self.final_states, self.returns, self.trajectory, self.reward_logits, self.best = final_states, returns, trajectory, reward_logits, best
         self.goal_dist = goal_dist
+
+
+class ActionAccuracy(object):
+    """What LatentDynamics.action_accuracy returns, from the counters of srlz_invfit_eval (rows, correct, bad, support[A], hits[A])."""
+    __slots__ = ("count", "accuracy", "majority_accuracy", "recall", "support", "hits", "loss", "route")
+
+    def __init__(self, counts, loss_sum, n_actions, route):
+        c = [int(v) for v in counts]
+        a = int(n_actions)
+        self.count, self.support, self.hits, self.route = c[0], c[3:3 + a], c[3 + a:3 + 2 * a], route
+        self.accuracy, self.majority_accuracy = float(c[1]) / c[0], float(max(self.support)) / c[0]
+        self.recall = [(float(h) / s if s else None) for h, s in zip(self.hits, self.support)]
+        self.loss = loss_sum / c[0]
 
 
 def _dynamics_owner(model):
@@ -1220,6 +1242,7 @@ class LatentDynamics(object):
         self._forced_model = route is not None
         self.fit = None  # the ForwardFit of the last refit_forward / from_recording
         self.reward_fit = None  # the RewardFit of the last refit_reward / from_recording(rewards=)
+        self.inverse_fit = None  # the InverseFit of the last refit_inverse / from_recording(inverse_fit=)
         self.device = next(self.owner.forward_net.parameters()).device
         if self.device.type != "cuda":
             raise C.SrlzError("LatentDynamics: the model must live on the GPU (there is no CPU path)")
@@ -1256,7 +1279,7 @@ class LatentDynamics(object):
 
     @classmethod
     def from_recording(cls, states, actions, episode_starts, n_actions=None, ridge=1e-6, starts=None, max_rows=8192, max_horizon=32,
-                       rewards=None, reward_fit=None):
+                       rewards=None, reward_fit=None, inverse_fit=None):
         """Dynamics for a representation that has no network behind it (PCA, supervised or ground-truth states, a model trained
         without the forward loss): the three heads alone (srlz.dynfit.heads_only_modules, losses = ["forward"], no encoder), the
         forward head fitted to the recording in closed form (srlz.dynfit.fit_forward; the arguments are its own).  The route is the
@@ -1264,27 +1287,37 @@ class LatentDynamics(object):
         planning works on the distance term alone; with `rewards` [N] the forward fit is followed by refit_reward on the same
         transitions (reward_fit: a dict of srlz.headfit.fit_reward keyword arguments; `starts`, when given, are its training
         transitions too, and its validation transitions are then the recording's other transitions unless reward_fit names them), "reward" joins the heads and plan, search and rollout work without a goal.  The inverse head is untrained
-        and stays unused either way.  The fits are kept as .fit and .reward_fit."""
+        and stays unused with the default inverse_fit=None; with a dict of srlz.invfit.fit_inverse keyword arguments (an empty one
+        for the defaults) the forward fit is followed by refit_inverse on the recording's actions, `starts` and the validation
+        transitions chosen by the rule reward_fit follows; "inverse" joins the heads, and action_logits and action_accuracy work.
+        The fits are kept as .fit, .reward_fit and .inverse_fit."""
         from . import dynfit
         from models.learner import _requireGpu
+        if inverse_fit is not None and not isinstance(inverse_fit, dict):
+            raise ValueError("inverse_fit must be None or a dict of srlz.invfit.fit_inverse keyword arguments (an empty one for the "
+                             "defaults), got %s" % type(inverse_fit).__name__)
         _requireGpu(True)
         fit = dynfit.fit_forward(states, actions, episode_starts, n_actions=n_actions, ridge=ridge, starts=starts)
         model = dynfit.heads_only_modules(fit.state_dim, fit.n_actions).to(torch.device("cuda", torch.cuda.current_device()))
         model.eval()
         dyn = cls(model, max_rows=max_rows, max_horizon=max_horizon)
         dyn._install_fit(fit)
-        if rewards is not None:
-            kw = dict(reward_fit or {})
+
+        def sides(given, name):
+            kw = dict(given or {})
             if starts is not None and "starts" not in kw:
                 kw["starts"] = starts
                 if "val_starts" not in kw:  # the recording's other transitions: never the ones the head is trained on
-                    from . import dynfit
                     rest = np.setdiff1d(dynfit.transitions(episode_starts), np.asarray(dynfit._host(starts)).reshape(-1))
                     if rest.size < 1:
-                        raise ValueError("starts lists every transition of the recording: the reward fit has none left to pick its "
-                                         "epoch on (give reward_fit=dict(val_starts=...), or fewer starts)")
+                        raise ValueError("starts lists every transition of the recording: the %s fit has none left to pick its "
+                                         "epoch on (give %s_fit=dict(val_starts=...), or fewer starts)" % (name, name))
                     kw["val_starts"] = rest.astype(np.int32)
-            dyn.refit_reward(states, rewards, episode_starts, **kw)
+            return kw
+        if inverse_fit is not None:
+            dyn.refit_inverse(states, actions, episode_starts, **sides(inverse_fit, "inverse"))
+        if rewards is not None:
+            dyn.refit_reward(states, rewards, episode_starts, **sides(reward_fit, "reward"))
         elif reward_fit is not None:
             raise ValueError("reward_fit configures the fit of the reward head: it needs rewards=")
         return dyn
@@ -1344,8 +1377,99 @@ class LatentDynamics(object):
         self.reward_fit = fit
         return fit
 
+    def _inverse_head(self):
+        """("linear" | "mlp" | None, the head's A): what owner.inverse_net is, in the words of --inverse-model-type."""
+        net = getattr(self.owner, "inverse_net", None)
+        s = self.state_dim
+        if isinstance(net, torch.nn.Linear) and net.bias is not None and net.in_features == 2 * s:
+            return "linear", net.out_features
+        if isinstance(net, torch.nn.Sequential) and len(net) == 5 and all(isinstance(net[i], torch.nn.Linear) and net[i].bias is not None
+                                                                          for i in (0, 2, 4)):
+            from . import invfit
+            h = invfit.MLP_HIDDEN
+            if (net[0].in_features, net[0].out_features, net[2].in_features, net[2].out_features, net[4].in_features) == (2 * s, h, h, h, h):
+                return "mlp", net[4].out_features
+        return None, 0
+
+    def refit_inverse(self, states, actions, episode_starts, **fit_kwargs):
+        """Train the inverse head on a recorded sequence (srlz.invfit.fit_inverse; n_actions and inverse_model_type are the head's
+        own, the other keyword arguments are fit_inverse's) and copy the kept epoch's parameters into owner.inverse_net IN PLACE,
+        under no_grad -> the InverseFit, kept as .inverse_fit.  "inverse" joins self.heads, whatever the model's losses trained;
+        action_logits and action_accuracy read the head at every call, nothing has to be refreshed.  A linear head within
+        srlz_invfit_supported is fitted by route "kernel", an `mlp` head (H = 128) and larger shapes by route "torch".  ValueError
+        when the recording's state_dim is not the head's, when inverse_net is neither of the reference's two heads, when n_actions=
+        or inverse_model_type= name another head; fit_inverse's ValueErrors as they are."""
+        from . import invfit
+        if not isinstance(states, (np.ndarray, torch.Tensor)) or len(states.shape) != 2 or states.shape[1] != self.state_dim:
+            raise ValueError("the recording's states of shape %s do not match the head's state_dim = %d"
+                             % (tuple(getattr(states, "shape", ())), self.state_dim))
+        kind, a = self._inverse_head()
+        if kind is None:
+            raise ValueError("refit_inverse needs the reference's inverse head, Linear(2S,A) or Linear(2S,128)-ReLU-Linear(128,128)-"
+                             "ReLU-Linear(128,A), with biases; this model's inverse_net is something else")
+        if fit_kwargs.get("n_actions") is None:
+            fit_kwargs["n_actions"] = a
+        if int(fit_kwargs["n_actions"]) != a:
+            raise ValueError("n_actions=%r is not the head's own %d" % (fit_kwargs["n_actions"], a))
+        if fit_kwargs.setdefault("inverse_model_type", kind) != kind:
+            raise ValueError("inverse_model_type=%r is not the head's own %r" % (fit_kwargs["inverse_model_type"], kind))
+        fit = invfit.fit_inverse(states, actions, episode_starts, **fit_kwargs)
+        net = self.owner.inverse_net
+        with torch.no_grad():
+            for key, value in fit.state_dict.items():
+                target = net
+                for part in key.split("."):
+                    target = target[int(part)] if part.isdigit() else getattr(target, part)
+                target.copy_(value)
+        if "inverse" not in self.heads:
+            self.heads = tuple(h for h in HEADS if h in self.heads or h == "inverse")
+        self.inverse_fit = fit
+        return fit
+
+    def action_accuracy(self, states, actions, episode_starts, starts=None):
+        """How well the inverse head reads the recorded action off (states[i], states[i + 1]) -> ActionAccuracy: count, accuracy,
+        majority_accuracy (the share of the most frequent action: what a constant answer scores), recall / support / hits per action
+        (recall None for an action without a row), loss (the mean cross-entropy), route.  The transitions are `starts`, or every
+        frame whose successor belongs to its episode.  Needs a trained or fitted inverse head (the gating ValueError of
+        action_logits).  A linear head of SRLModules within srlz_invfit_supported is ONE srlz_invfit_eval launch (route "kernel");
+        anything else goes through the model's own inverseModel in batches of max_rows (route "model"), counted on the device.  An
+        argmax tie goes to the lowest action."""
+        from . import dynfit
+        from models.modules import SRLModules
+        self._need("inverse")
+        if not isinstance(states, (np.ndarray, torch.Tensor)) or len(states.shape) != 2 or states.shape[1] != self.state_dim:
+            raise ValueError("the recording's states of shape %s do not match the head's state_dim = %d"
+                             % (tuple(getattr(states, "shape", ())), self.state_dim))
+        kind, a = self._inverse_head()
+        if kind is None:
+            a = self.n_actions
+        labels, starts, _ = dynfit.check_fit_recording(states, actions, episode_starts, n_actions=a, starts=starts)
+        n, s = int(states.shape[0]), self.state_dim
+        x = self._device_states(states, n, False, False)
+        d_labels = torch.from_numpy(labels).to(self.device)
+        counts = torch.zeros(ops.invfit_n_counts(a), dtype=torch.int64, device=self.device)
+        loss = torch.zeros(1, dtype=torch.float64, device=self.device)
+        kernel = kind == "linear" and isinstance(self.owner, SRLModules) and not self._forced_model and ops.invfit_supported(s, a) \
+            and n * s < 2 ** 31
+        if kernel:
+            net = self.owner.inverse_net
+            with torch.no_grad():
+                flat = torch.cat((net.weight.detach().reshape(-1), net.bias.detach().reshape(-1))).float().contiguous()
+            ops.invfit_eval(ops.RewardProbeData(x, d_labels), torch.from_numpy(starts.reshape(1, -1)), a, flat, loss, counts)
+        else:
+            from . import invfit
+            d_starts = torch.from_numpy(starts).to(self.device).long()
+            with torch.no_grad():
+                for lo in range(0, d_starts.shape[0], self.max_rows):
+                    i = d_starts[lo:lo + self.max_rows]
+                    z, y = self.owner.inverseModel(x[i], x[i + 1]), d_labels[i].long()
+                    loss += torch.nn.functional.cross_entropy(z.double(), y, reduction="sum")
+                    counts += invfit._torch_counts(z, y, a)
+        c = counts.cpu().numpy()
+        return ActionAccuracy(c, float(loss.cpu()[0]), a, "kernel" if kernel else ROUTE_MODEL)
+
     def _need(self, head):
-        if head in self.heads:  # (refit_forward / refit_reward add their head to the heads the losses trained)
+        if head in self.heads:  # (refit_forward / refit_reward / refit_inverse add their head to the heads the losses trained)
             return
         check_head(self.owner, head, self.untrained_ok)
 

@@ -10,8 +10,8 @@ of a (S + A + 1)-square system.  The only work that grows with the dataset is G 
 route "gram" is csrc/dynfit.hip (fp64 MFMA, nothing materialised, reproducible bits, G exactly symmetric), route "torch" builds Z and
 Y in fp64 on the device and takes two matmuls — for shapes srlz_dynfit_supported refuses, or when forced for a measurement.  The
 small system is solved in fp64 numpy on the host.  DESIGN.md §3.20.  The reward head of the same representations has no closed
-form: srlz/headfit.py trains it on the recording (LatentDynamics.refit_reward, from_recording(rewards=)); the split by episodes and
-the heads-only module are shared with it.
+form: srlz/headfit.py trains it on the recording (LatentDynamics.refit_reward, from_recording(rewards=)), and srlz/invfit.py the
+inverse head (refit_inverse, from_recording(inverse_fit=)); the split by episodes and the heads-only module are shared with them.
 
 transitions, split_episodes and solve_forward_head are pure host functions: no GPU is asked for.
 """

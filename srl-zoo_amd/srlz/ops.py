@@ -2722,3 +2722,89 @@ def headfit_eval(data, idx, hidden, params, running_loss, counts, workspace=None
         _reward_probe_buffer(workspace, "workspace", torch.uint8, nbytes, data, who="headfit")
     C.headfit_eval(ptr(data.states), ptr(data.labels), data.n, data.s, h, ptr(tb.device), ctypes.c_void_p(tb.host.data_ptr()), n_batches,
                    b, ptr(params), ptr(running_loss), ptr(counts), ptr(workspace), workspace.numel(), ptr(ticket), stream())
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# The inverse head on a recorded sequence (csrc/invfit.hip; include/srlz.h states the layout, every sum's order and the limits):
+# an epoch of Adam steps in one launch, a validation phase in one more.  The data is a RewardProbeData of (states, actions) — the
+# labels are the actions and are NOT range-checked here: the kernels count a label outside [0, A) in `bad` and index nothing by it
+# (srlz/invfit.py checks host actions before it uploads them).  Tables are headfit_table's; the argument checks and error types are
+# those of the headfit wrappers.
+# ----------------------------------------------------------------------------------------------------------------
+INVFIT_COUNTS = ("rows", "correct", "bad")  # the first three int64 counters; support[A] and hits[A] follow
+
+
+def invfit_supported(s, a):
+    return bool(C.invfit_supported(int(s), int(a)))
+
+
+def invfit_n_params(s, a):
+    """Linear(2S, A) with its bias, flat in state_dict order (0 for S < 1 or A < 2)."""
+    return int(C.invfit_n_params(int(s), int(a)))
+
+
+def invfit_chunk_rows(s, a):
+    """Rows of a minibatch that srlz_invfit_fit processes at a time (a function of S and A alone; 0 for a refused shape)."""
+    return int(C.invfit_chunk_rows(int(s), int(a)))
+
+
+def invfit_n_counts(a):
+    """The length of the counters: rows, correct, bad, support[A], hits[A]."""
+    return len(INVFIT_COUNTS) + 2 * int(a)
+
+
+def _invfit_shape(data, n_actions):
+    if not isinstance(data, RewardProbeData):
+        raise ValueError("invfit: data must be a RewardProbeData of (states, actions)")
+    a = int(n_actions)
+    if not invfit_supported(data.s, a):
+        raise ValueError("invfit: state_dim %d with %d actions is outside srlz_invfit_supported" % (data.s, a))
+    return a
+
+
+def invfit_fit(data, idx, n_actions, params, m, v, t0, lr, running_loss, counts, step_loss=None, last_grad=None, betas=(0.9, 0.999),
+               eps=1e-8):
+    """idx.shape[0] consecutive Adam steps of the inverse head (Linear(2S, A), cross-entropy) in ONE launch of srlz_invfit_fit:
+    minibatch s is the rows [states[i] ; states[i + 1]] for i in idx[s], labelled labels[i].  No autograd: the kernel owns the
+    backward.  data: RewardProbeData(states fp32 [N,S], actions int32 [N]) on the device; idx: an int32 [n, B] host table or a
+    headfit_table; params / m / v: float32 [invfit_n_params(S, A)] on the device in state_dict order, updated in place; t0: the Adam
+    steps already taken; running_loss float64 [1] and counts int64 [invfit_n_counts(A)] are added to; step_loss: float64 [>= steps]
+    for the mean loss of every step, or None; last_grad: float32 [n_params] for the last step's gradient, or None."""
+    a = _invfit_shape(data, n_actions)
+    tb = headfit_table(data, idx)
+    n_steps, b = int(tb.host.shape[0]), int(tb.host.shape[1])
+    n_par = invfit_n_params(data.s, a)
+    for t, name in ((params, "params"), (m, "m"), (v, "v")):
+        _reward_probe_buffer(t, name, torch.float32, n_par, data, exact=True, who="invfit")
+    _reward_probe_buffer(running_loss, "running_loss", torch.float64, 1, data, who="invfit")
+    _reward_probe_buffer(counts, "counts", torch.int64, invfit_n_counts(a), data, exact=True, who="invfit")
+    if step_loss is not None:
+        _reward_probe_buffer(step_loss, "step_loss", torch.float64, n_steps, data, who="invfit")
+    if last_grad is not None:
+        _reward_probe_buffer(last_grad, "last_grad", torch.float32, n_par, data, exact=True, who="invfit")
+    C.invfit_fit(ptr(data.states), ptr(data.labels), data.n, data.s, a, ptr(tb.device), ctypes.c_void_p(tb.host.data_ptr()), n_steps, b,
+                 ptr(params), ptr(m), ptr(v), int(t0), float(lr), float(betas[0]), float(betas[1]), float(eps), ptr(running_loss),
+                 ptr(counts), ptr(step_loss), ptr(last_grad), stream())
+
+
+def invfit_eval(data, idx, n_actions, params, running_loss, counts, workspace=None):
+    """The forward, loss (float64 per row) and counts of idx.shape[0] minibatches in ONE launch of srlz_invfit_eval; params are only
+    read, running_loss and counts (int64 [invfit_n_counts(A)]) are added to.  workspace: a contiguous uint8 device tensor of at least
+    srlz_invfit_eval_workspace(n, B) bytes, made here when None."""
+    a = _invfit_shape(data, n_actions)
+    tb = headfit_table(data, idx)
+    n_batches, b = int(tb.host.shape[0]), int(tb.host.shape[1])
+    _reward_probe_buffer(params, "params", torch.float32, invfit_n_params(data.s, a), data, exact=True, who="invfit")
+    _reward_probe_buffer(running_loss, "running_loss", torch.float64, 1, data, who="invfit")
+    _reward_probe_buffer(counts, "counts", torch.int64, invfit_n_counts(a), data, exact=True, who="invfit")
+    device = data.states.device
+    ticket = _REWARD_PROBE_TICKET.get(device.index)
+    if ticket is None:
+        ticket = _REWARD_PROBE_TICKET[device.index] = torch.zeros(1, dtype=torch.int32, device=device)
+    nbytes = int(C.invfit_eval_workspace(n_batches, b))
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=device)
+    else:
+        _reward_probe_buffer(workspace, "workspace", torch.uint8, nbytes, data, who="invfit")
+    C.invfit_eval(ptr(data.states), ptr(data.labels), data.n, data.s, a, ptr(tb.device), ctypes.c_void_p(tb.host.data_ptr()), n_batches,
+                  b, ptr(params), ptr(running_loss), ptr(counts), ptr(workspace), workspace.numel(), ptr(ticket), stream())
