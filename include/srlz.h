@@ -1292,6 +1292,96 @@ int srlz_invfit_eval(const float* states /*[N,S]*/, const int* labels /*[N]*/, i
                      long long* counts /*[3 + 2A]*/, void* ws, size_t ws_bytes, unsigned* ticket, srlz_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The robotic priors (csrc/robotic.hip): roboticPriorsLoss of the reference, losses/losses.py:62-99 — temporal coherence,
+ * causality, proportionality and repeatability of one minibatch of states, over the pair lists of losses/utils.py:75-116
+ * (findPriorsPairs; srl-zoo_amd/losses/utils.py here).  states, next_states: fp32 [B, S].  With D_b = next_states[b] - states[b],
+ * n_b = |D_b|, e_ij = exp(-|s_i - s_j|^2), `dis` the dissimilar pairs [n_dis, 2] and `same` the same-action pairs [n_same, 2]
+ * (int32 positions inside the minibatch, in any order, duplicates, i > j and i == j allowed):
+ *   terms[0] temporal coherence = mean_b n_b^2            (losses.py:78-81)
+ *   terms[1] causality          = mean_dis e_ij            (losses.py:80, 82-83)
+ *   terms[2] proportionality    = mean_same (n_i - n_j)^2  (losses.py:84-85)
+ *   terms[3] repeatability      = mean_same e_ij |D_i - D_j|^2   (losses.py:87-90)
+ * fwd: ONE launch of one workgroup of 256 threads.  Order of every sum, a function of (B, S, n_dis, n_same) alone: a row's or a
+ *   pair's value in fp32, k ascending with fma; thread t adds rows t, t + 256, .. (pairs likewise, list order) in fp64; a wave adds
+ *   by a butterfly (offsets 32 .. 1); the four wave sums are added left to right; then the division by the count.  terms: four
+ *   fp64 values; terms32: the same, rounded to fp32; norms [B]: the n_b, kept for the backward.
+ * bwd: ONE launch that writes dstates and dnext_states [B, S] whole, one thread per element:
+ *   d next_states[r] = g_tc 2 D_r / B + sum over r's same-action partners q of
+ *                        g_pr 2 (n_r - n_q) / n_r / n_same D_r   (nothing where n_r = 0, as torch.norm's backward)
+ *                      + g_re 2 e_rq / n_same (D_r - D_q)
+ *   d states[r]      = - d next_states[r] - sum over the same-action partners of g_re 2 e_rq |D_r - D_q|^2 / n_same (s_r - s_q)
+ *                                         - sum over the dissimilar partners  of g_ca 2 e_rq / n_dis (s_r - s_q)
+ *   Both ends of a pair receive the same expression, so the kernel reads an INCIDENCE table per list, which the host builds
+ *   (srlz/ops.py robotic_incidence): int32 offsets [B + 1], then 2 * n partners; pair p = [i, j] gives row i the partner j and
+ *   row j the partner i (i == j: twice itself, which adds zero), a row's partners in pair order.  The thread adds its same-action
+ *   partners in table order, then the dissimilar ones, in fp64; the pair scalars are recomputed by every thread, k ascending, so
+ *   the cost is S^2 per incidence: the loss is meant for states of a few dimensions.  g_*: four fp32 device scalars, the upstream
+ *   gradients of the four terms.  No atomics; two calls give identical bits.
+ * Every index read on the device is clamped to the tensor it addresses (pair entries and partners to [0, B), offsets to
+ *   [0, 2n]); the host checks the lists before it uploads them.
+ * Refused before anything is enqueued, nothing written: B < 1, S < 1, B * S >= 2^31, an empty pair list (the reference's mean of
+ *   nothing is NaN) or 2^30 pairs: SRLZ_ERR_BAD_DESC; a missing pointer: SRLZ_ERR_NULL.
+ * ------------------------------------------------------------------------------------------------------------ */
+int srlz_robotic_fwd(const float* states, const float* next_states, int B, int S, const int* dis /*[n_dis,2]*/, int n_dis,
+                     const int* same /*[n_same,2]*/, int n_same, float* norms /*[B]*/, double* terms /*[4]*/,
+                     float* terms32 /*[4]*/, srlz_stream_t stream);
+int srlz_robotic_bwd(const float* states, const float* next_states, const float* norms /*[B]*/, int B, int S,
+                     const int* same_incidence /*[B + 1 + 2 n_same]*/, int n_same, const int* dis_incidence /*[B + 1 + 2 n_dis]*/,
+                     int n_dis, const float* g_tc, const float* g_ca, const float* g_pr, const float* g_re, float* dstates,
+                     float* dnext_states, srlz_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * A linear state map fitted on a recording by the robotic priors alone (csrc/robotic.hip, srlz/priorsfit.py): s = W x + b with
+ * W [S, D] — nn.Linear(D, S) under roboticPriorsLoss (losses/losses.py:62-99, weight 1 each) and torch.optim.Adam, the learner's
+ * loop (models/learner.py:277-297, 420-489) without its encoder.  features: fp32 [N, D]; row b of minibatch k is the transition
+ * (features[i], features[i + 1]) with i = idx[k][b] clamped to [0, N - 2].  params, m, v: fp32 [S * D + S] in state_dict order
+ * (weight, bias).  The pair tables of ALL minibatches live in ONE int32 buffer `tables` [tables_len]; `dir` [n_minibatches][6]
+ * names, per minibatch: the offset of its dissimilar pairs [n_dis, 2], n_dis, the offset of its same-action pairs [n_same, 2],
+ * n_same, the offsets of the two incidence tables (srlz_robotic_bwd's format: [B + 1] offsets, then the partners).  `order` lists
+ * the minibatch ids a call walks.  idx, dir and order are passed twice: the device copy the kernel reads and a host copy the
+ * entry point checks.
+ * fit: n_steps consecutive Adam steps in ONE launch of ONE workgroup of 256 threads; parameters and gradient stay in LDS from the
+ *   first step to the last, the moments in global memory.  Order of every sum, a function of (D, S, B) and the tables alone:
+ *   states — 16 lanes per feature row, lane kk adds d = kk, kk + 16, .. ascending, a butterfly over the 16 lanes (offsets 8 .. 1),
+ *   + bias; the four terms and the gradient with respect to both state tiles — as srlz_robotic_fwd / _bwd with upstream gradients
+ *   1; every parameter's gradient — one thread per element, b ascending, the x_i product before the x_{i+1} product (fma); Adam —
+ *   the arithmetic of srlz_adam_step, the step scalars evaluated in double from t0 + step.  running [4] += the four terms of every
+ *   step (fp64); step_terms (may be NULL) receives [n_steps][4]; last_grad (may be NULL) the gradient of the LAST step.  No float
+ *   atomics.  Two calls leave identical bits; n steps in one call and n calls of one step leave identical bits in params, m, v,
+ *   running and step_terms.
+ * eval: one workgroup per listed minibatch, the same states and terms; the terms go to ws (srlz_robotic_eval_workspace(n) bytes)
+ *   and are added to running [4] in LIST order by the workgroup that finishes last (`ticket`: one zeroed unsigned the kernel leaves
+ *   zeroed; no spinning, no grid barrier): the result does not depend on which workgroup that is.  params are only read.
+ * Limits: the LDS budget and nothing else.  With SPAD = (S rounded up to a multiple of 4) | 4 the LDS image of the parameters holds
+ *   (D + 1) * SPAD floats (row d < D is W[:, d], row D the bias; pads zero and never written back), the gradient as many, Adam's
+ *   table 512, the four tiles (states, next states, their gradients) B * SPAD each, the norms B rounded up to 4 and the block sums' 32, within the
+ *   160 KB srlz_headfit_fit uses:
+ *   srlz_robotic_supported(D, S, B) = D, S, B >= 1 and 2 * (D + 1) * SPAD + 512 + 4 * B * SPAD + ((B + 3) & ~3) + 32 <= 40960.
+ *   That accepts D <= 200 with S <= 8 and B <= 256 (17 912 floats at the three ends), D = 768 with S <= 12 at B = 256, D = 4983
+ *   at S = 3 with B = 32, and refuses D = 4984 there.
+ * Every index read on the device is clamped: rows to [0, N - 2], minibatch ids to [0, n_minibatches), table offsets and counts so
+ *   that a list lies inside [0, tables_len), pair entries and partners to [0, B).
+ * Refused before anything is enqueued, nothing written: an unsupported (D, S, B), N < 2, N * D >= 2^31, no minibatch, no step,
+ *   n_minibatches * B >= 2^31, t0 < 0, an entry of idx_host outside [0, N - 2], of order_host outside [0, n_minibatches), a
+ *   directory entry with an empty list or one reaching outside the tables: SRLZ_ERR_BAD_DESC; a missing pointer SRLZ_ERR_NULL;
+ *   ws_bytes below srlz_robotic_eval_workspace: SRLZ_ERR_WORKSPACE.  srlz_robotic_eval_workspace returns 0 for n < 1.
+ * ------------------------------------------------------------------------------------------------------------ */
+int srlz_robotic_supported(int D, int S, int B);
+long long srlz_robotic_n_params(int D, int S); /* S*D + S; 0 for D < 1 or S < 1 */
+int srlz_robotic_fit(const float* features /*[N,D]*/, int N, int D, int S, const int* idx /*[n_minibatches,B]*/,
+                     const int* idx_host, int n_minibatches, int B, const int* tables /*[tables_len]*/, int tables_len,
+                     const int* dir /*[n_minibatches,6]*/, const int* dir_host, const int* order /*[n_steps]*/,
+                     const int* order_host, int n_steps, float* params, float* m, float* v, int t0, double lr, double beta1,
+                     double beta2, double eps, double* running /*[4]*/, double* step_terms /*[n_steps,4] or NULL*/,
+                     float* last_grad /*[P] or NULL*/, srlz_stream_t stream);
+size_t srlz_robotic_eval_workspace(int n);
+int srlz_robotic_eval(const float* features /*[N,D]*/, int N, int D, int S, const int* idx /*[n_minibatches,B]*/,
+                      const int* idx_host, int n_minibatches, int B, const int* tables /*[tables_len]*/, int tables_len,
+                      const int* dir /*[n_minibatches,6]*/, const int* dir_host, const int* order /*[n]*/, const int* order_host,
+                      int n, const float* params, double* running /*[4]*/, void* ws, size_t ws_bytes, unsigned* ticket,
+                      srlz_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Debug / calibration hooks (not on the product path).
  * ------------------------------------------------------------------------------------------------------------ */
 /* Host-only: dump the virtual-grid program of a 64->64 convolution (tests interpret it on the CPU).

@@ -1,8 +1,9 @@
-"""LossManager and the hot-path losses (reference losses/losses.py:19-59, 102-170, 172-214, 239-256, 290-359, 360-376).
+"""LossManager and the hot-path losses (reference losses/losses.py:19-59, 62-99, 102-170, 172-214, 239-256, 290-359, 360-376).
 
 Same function names, argument order and return values as the reference; the reductions and their gradients run as
-fused HIP kernels (srlz/ops.py).  The reward prior and the episode prior run on csrc/priors.hip; the robotic-priors loss
-(`priors`, with its pair mining) and the mutual-information loss are outside the hot path and not provided.
+fused HIP kernels (srlz/ops.py).  The reward prior and the episode prior run on csrc/priors.hip, the robotic priors on
+csrc/robotic.hip over the pairs of losses/utils.py (the trainer's `--losses priors` is still rejected: models/learner.py); the
+mutual-information loss is outside the hot path and not provided.
 """
 from __future__ import print_function, division, absolute_import
 
@@ -165,6 +166,31 @@ def rewardPriorLoss(states, rewards_st, weight, loss_manager):
     reward_prior_loss = ops.RewardPriorFn.apply(states, rewards_st)
     loss_manager.addToLosses('reward_prior', weight, reward_prior_loss)
     return _returned(reward_prior_loss, weight, loss_manager)
+
+
+def roboticPriorsLoss(states, next_states, minibatch_idx, dissimilar_pairs, same_actions_pairs, weight, loss_manager):
+    """The four robotic priors: temporal coherence, causality, proportionality, repeatability (reference losses.py:62-99), logged
+    under the reference's four names with weight 1 each; returns weight * (their sum).
+    :param states: (th.Tensor) fp32 [B, S] on the device
+    :param next_states: (th.Tensor)
+    :param minibatch_idx: (int)
+    :param dissimilar_pairs: ([np.ndarray]) per minibatch, as losses.utils.findPriorsPairs returns them; an entry may also be the
+        ops.RoboticTable of its minibatch (ops.robotic_table: checked and uploaded once), which is then shared with same_actions_pairs.
+        Plain lists are host work on EVERY call: both lists are checked, both incidence tables built and all four uploaded
+    :param same_actions_pairs: ([np.ndarray])
+    :param weight: coefficient to weight the loss
+    :param loss_manager: (LossManager)
+    ValueError: an empty pair list (the reference's mean of nothing is NaN), a pair index outside [0, B)."""
+    table = dissimilar_pairs[minibatch_idx]
+    if not isinstance(table, ops.RoboticTable):
+        table = ops.robotic_table(table, same_actions_pairs[minibatch_idx], states.shape[0], states.device)
+    losses = ops.RoboticPriorsFn.apply(states, next_states, table)
+    for name, loss in zip(ops.ROBOTIC_TERMS, losses):
+        loss_manager.addToLosses(name, 1, loss)
+    if getattr(loss_manager, "collect_only", False):
+        return None
+    # 0 + l0 + l1 + l2 + l3 left to right, then weight * total: the reference's two roundings, one launch each
+    return ops.weighted(ops.TotalLossFn.apply((1.0, 1.0, 1.0, 1.0), None, *losses), weight)
 
 
 def sampleEpisodeOthers(episodes, balanced_sampling):

@@ -2,7 +2,8 @@
 (priors.py:71-102) and SRLLinear (priors.py:105-125), the `--model-type mlp | linear` models of the losses that need no decoder
 (inverse / forward / reward).  Their nn.Linear(input_dim, .) runs on csrc/dense.hip.  Also the episode prior's Discriminator and
 ReverseLayerF (priors.py:129-175): the discriminator holds the parameters, its forward and backward run inside ops.EpisodePriorFn
-(csrc/priors.hip).  The robotic-priors loss (`priors`) stays outside this build."""
+(csrc/priors.hip).  The robotic-priors loss (`priors`) is losses.losses.roboticPriorsLoss on csrc/robotic.hip and is fitted on a
+recording by srlz/priorsfit.py; the trainer still rejects `--losses priors`."""
 from __future__ import print_function, division, absolute_import
 
 import torch as th

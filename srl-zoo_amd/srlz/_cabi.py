@@ -312,6 +312,14 @@ _PROTOS = {
                                 P, P, P, P, P]),
     "srlz_invfit_eval_workspace": (c_size_t, [c_int, c_int]),
     "srlz_invfit_eval": (c_int, [P, P, c_int, c_int, c_int, P, P, c_int, c_int, P, P, P, P, c_size_t, P, P]),
+    "srlz_robotic_fwd": (c_int, [P, P, c_int, c_int, P, c_int, P, c_int, P, P, P, P]),
+    "srlz_robotic_bwd": (c_int, [P, P, P, c_int, c_int, P, c_int, P, c_int, P, P, P, P, P, P, P]),
+    "srlz_robotic_supported": (c_int, [c_int, c_int, c_int]),
+    "srlz_robotic_n_params": (c_longlong, [c_int, c_int]),
+    "srlz_robotic_fit": (c_int, [P, c_int, c_int, c_int, P, P, c_int, c_int, P, c_int, P, P, P, P, c_int, P, P, P, c_int, c_double,
+                                 c_double, c_double, c_double, P, P, P, P]),
+    "srlz_robotic_eval_workspace": (c_size_t, [c_int]),
+    "srlz_robotic_eval": (c_int, [P, c_int, c_int, c_int, P, P, c_int, c_int, P, c_int, P, P, P, P, c_int, P, P, P, c_size_t, P, P]),
 }
 
 # entry points whose int return value is data, not a status
@@ -328,7 +336,7 @@ _NOT_STATUS = {"srlz_version", "srlz_device_cus", "srlz_conv64_fwd_tiles", "srlz
                "srlz_rollout_tile", "srlz_plan_supported", "srlz_rollout_goal_supported", "srlz_plan_goal_supported",
                "srlz_horizon_supported", "srlz_beam_supported", "srlz_beam_leaves", "srlz_dynfit_supported",
                "srlz_dynfit_chunk_rows", "srlz_headfit_supported", "srlz_headfit_chunk_rows", "srlz_invfit_supported",
-               "srlz_invfit_chunk_rows"}
+               "srlz_invfit_chunk_rows", "srlz_robotic_supported"}
 
 EXPORTED = sorted(_PROTOS.keys())
 

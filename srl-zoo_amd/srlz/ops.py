@@ -8,6 +8,8 @@ last transposed conv; images and everything the caller sees stay in the referenc
 import ctypes
 import weakref
 
+import numpy as np
+
 import torch
 from torch.autograd import Function
 
@@ -2808,3 +2810,248 @@ def invfit_eval(data, idx, n_actions, params, running_loss, counts, workspace=No
         _reward_probe_buffer(workspace, "workspace", torch.uint8, nbytes, data, who="invfit")
     C.invfit_eval(ptr(data.states), ptr(data.labels), data.n, data.s, a, ptr(tb.device), ctypes.c_void_p(tb.host.data_ptr()), n_batches,
                   b, ptr(params), ptr(running_loss), ptr(counts), ptr(workspace), workspace.numel(), ptr(ticket), stream())
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# The robotic priors (csrc/robotic.hip): roboticPriorsLoss, reference losses/losses.py:62-99
+# ----------------------------------------------------------------------------------------------------------------
+ROBOTIC_TERMS = ("temp_coherence_loss", "causality_loss", "proportionality_loss", "repeatability_loss")  # losses.py:92
+
+
+def robotic_pairs(pairs, batch, name="pairs"):
+    """A pair list as the kernels read it: int32 [n, 2], checked on the host.  Any order, duplicates, i > j and i == j are allowed.
+    ValueError: an empty list (the reference's mean of nothing is NaN), another shape, non-integers, an index outside [0, batch)."""
+    a = np.asarray(pairs)
+    if a.size == 0:
+        raise ValueError("robotic priors: the %s list is empty: the mean over no pair is NaN" % name)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError("robotic priors: the %s must be an [n, 2] list of positions, got shape %s" % (name, a.shape))
+    if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("robotic priors: the %s must be integers (got %s)" % (name, a.dtype))
+    if a.shape[0] >= 2 ** 30:
+        raise ValueError("robotic priors: fewer than 2^30 %s are supported" % name)
+    lo, hi = int(a.min()), int(a.max())
+    if lo < 0 or hi >= int(batch):
+        raise ValueError("robotic priors: the %s must lie in [0, %d), got %d .. %d" % (name, int(batch), lo, hi))
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def robotic_incidence(pairs, batch):
+    """The incidence table srlz_robotic_bwd walks (include/srlz.h): int32 [batch + 1 + 2n] — offsets [batch + 1], then the partners.
+    Pair p = [i, j] gives row i the partner j and row j the partner i (i == j: twice itself); a row's partners stand in pair order,
+    the i end of a pair before its j end.  Pure host function."""
+    p = robotic_pairs(pairs, batch)
+    rows, partners = p.reshape(-1), p[:, ::-1].reshape(-1)  # (i0, j0, i1, j1, ..) and (j0, i0, j1, i1, ..)
+    order = np.argsort(rows, kind="stable")
+    offsets = np.zeros(int(batch) + 1, np.int64)
+    np.cumsum(np.bincount(rows, minlength=int(batch)), out=offsets[1:])
+    return np.concatenate((offsets, partners[order])).astype(np.int32)
+
+
+class RoboticTable(object):
+    """The pair lists of ONE minibatch on the device, built and uploaded once (robotic_table): dis / same int32 [n, 2], their
+    incidence tables, the counts and the batch size they were checked for."""
+    __slots__ = ("batch", "n_dis", "n_same", "dis", "same", "dis_inc", "same_inc", "buffer")
+
+
+def robotic_table(dissimilar_pairs, same_actions_pairs, batch, device):
+    """Check both pair lists of a minibatch of `batch` rows on the host (robotic_pairs' ValueErrors), build both incidence tables
+    and upload the four as ONE int32 buffer -> RoboticTable."""
+    batch = int(batch)
+    dis, same = robotic_pairs(dissimilar_pairs, batch, "dissimilar pairs"), robotic_pairs(same_actions_pairs, batch, "same-action pairs")
+    parts = (dis.reshape(-1), same.reshape(-1), robotic_incidence(dis, batch), robotic_incidence(same, batch))
+    host = torch.from_numpy(np.concatenate(parts))
+    if torch.device(device).type == "cuda":
+        host = host.pin_memory()
+    buf = host.to(device, non_blocking=True)
+    t = RoboticTable()
+    t.batch, t.n_dis, t.n_same, t.buffer = batch, int(dis.shape[0]), int(same.shape[0]), buf
+    off = 0
+    for name, part in zip(("dis", "same", "dis_inc", "same_inc"), parts):
+        setattr(t, name, buf[off:off + part.size])
+        off += part.size
+    return t
+
+
+class RoboticPriorsFn(Function):
+    """The four robotic priors of one minibatch -> (temporal coherence, causality, proportionality, repeatability), four 0-dim fp32
+    tensors (views of one [4] tensor) — roboticPriorsLoss, reference losses/losses.py:62-99.  `table`: a RoboticTable for this batch
+    size.  One launch forward (fp64 sums in one order, rounded once to fp32; robotic_priors_terms gives the fp64 values), one launch
+    backward that writes both gradients whole, no atomics: two calls give identical bits."""
+
+    @staticmethod
+    def forward(ctx, states, next_states, table):
+        terms32, _terms64, norms = _robotic_forward(states, next_states, table)
+        ctx.save_for_backward(_check(states, "states"), _check(next_states, "next_states"), norms)
+        ctx.table = table
+        return tuple(terms32.unbind(0))
+
+    @staticmethod
+    def backward(ctx, g_tc, g_ca, g_pr, g_re):
+        states, next_states, norms = ctx.saved_tensors
+        t = ctx.table
+        b, s = states.shape
+        gs = [_check(g, "loss grad") for g in (g_tc, g_ca, g_pr, g_re)]
+        ds, dns = torch.empty_like(states), torch.empty_like(next_states)
+        C.robotic_bwd(ptr(states), ptr(next_states), ptr(norms), b, s, ptr(t.same_inc), t.n_same, ptr(t.dis_inc), t.n_dis,
+                      ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(gs[3]), ptr(ds), ptr(dns), stream())
+        return ds, dns, None
+
+
+def _robotic_forward(states, next_states, table):
+    states, next_states = _check(states, "states"), _check(next_states, "next_states")
+    if states.dim() != 2 or states.shape != next_states.shape:
+        raise ValueError("robotic priors: states and next_states must both be [B, S], got %s and %s"
+                         % (tuple(states.shape), tuple(next_states.shape)))
+    if not isinstance(table, RoboticTable):
+        raise ValueError("robotic priors: the pair lists must be a RoboticTable (ops.robotic_table)")
+    b, s = states.shape
+    if table.batch != b or table.buffer.device != states.device:
+        raise ValueError("robotic priors: the table was built for %d rows on %s, the states have %d rows on %s"
+                         % (table.batch, table.buffer.device, b, states.device))
+    terms64 = torch.empty(4, dtype=torch.float64, device=states.device)
+    terms32 = torch.empty(4, dtype=torch.float32, device=states.device)
+    norms = torch.empty(b, dtype=torch.float32, device=states.device)
+    C.robotic_fwd(ptr(states), ptr(next_states), b, s, ptr(table.dis), table.n_dis, ptr(table.same), table.n_same, ptr(norms),
+                  ptr(terms64), ptr(terms32), stream())
+    return terms32, terms64, norms
+
+
+def robotic_priors_terms(states, next_states, table):
+    """The four terms as the forward launch sums them: a float64 [4] device tensor, no autograd."""
+    return _robotic_forward(states.detach(), next_states.detach(), table)[1]
+
+
+def robotic_supported(d, s, b):
+    """srlz_robotic_supported: D features, state dimension S and minibatches of B fit the LDS budget of srlz_robotic_fit."""
+    return bool(C.robotic_supported(int(d), int(s), int(b)))
+
+
+def robotic_n_params(d, s):
+    """Linear(D, S) with its bias, flat in state_dict order (0 for D < 1 or S < 1)."""
+    return int(C.robotic_n_params(int(d), int(s)))
+
+
+class _HostDevice(object):
+    """An int32 table as the fit's entry points take it: the host copy they check and the device copy the kernels read."""
+    __slots__ = ("host", "device")
+
+    def __init__(self, host, device):
+        self.host = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32))
+        pinned = self.host.pin_memory() if torch.device(device).type == "cuda" else self.host
+        self.device = pinned.to(device, non_blocking=True)
+
+    def host_ptr(self):
+        return ctypes.c_void_p(self.host.data_ptr())
+
+
+class RoboticFitTables(object):
+    """Everything srlz_robotic_fit / _eval read besides the features, built and uploaded ONCE per fit (robotic_fit_tables): idx
+    [n, B] (the frames of every minibatch), tables (all pair lists and incidence tables), dir [n, 6]."""
+    __slots__ = ("n", "batch", "idx", "tables", "dir")
+
+
+def robotic_fit_tables(minibatches, dissimilar_pairs, same_actions_pairs, device):
+    """minibatches: n arrays of B frame indices (as losses.utils.priors_pairs leaves them); the two pair lists per minibatch.  The
+    pair lists are checked here (robotic_pairs' ValueErrors); the frame indices by the entry points, against the features."""
+    mb = np.asarray(minibatches)
+    if mb.ndim != 2 or mb.shape[0] < 1 or mb.shape[1] < 1 or not np.issubdtype(mb.dtype, np.integer):
+        raise ValueError("robotic fit: the minibatches must be an integer [n, B] table, got %s %s" % (mb.dtype, mb.shape))
+    n, b = int(mb.shape[0]), int(mb.shape[1])
+    if len(dissimilar_pairs) != n or len(same_actions_pairs) != n:
+        raise ValueError("robotic fit: %d minibatches, but %d and %d pair lists" % (n, len(dissimilar_pairs), len(same_actions_pairs)))
+    if mb.min() < 0 or mb.max() >= 2 ** 31 - 1:
+        raise ValueError("robotic fit: frame indices must lie in [0, 2^31 - 1)")
+    parts, entries, off = [], np.zeros((n, 6), np.int64), 0
+    for k in range(n):
+        dis = robotic_pairs(dissimilar_pairs[k], b, "dissimilar pairs of minibatch %d" % k)
+        same = robotic_pairs(same_actions_pairs[k], b, "same-action pairs of minibatch %d" % k)
+        four = (dis.reshape(-1), same.reshape(-1), robotic_incidence(dis, b), robotic_incidence(same, b))
+        offs = off + np.concatenate(([0], np.cumsum([p.size for p in four])))
+        entries[k] = (offs[0], dis.shape[0], offs[1], same.shape[0], offs[2], offs[3])
+        off = int(offs[4])
+        parts.extend(four)
+    if off >= 2 ** 31:
+        raise ValueError("robotic fit: the pair tables hold %d entries, 2^31 or more" % off)
+    t = RoboticFitTables()
+    t.n, t.batch = n, b
+    t.idx, t.tables, t.dir = _HostDevice(mb, device), _HostDevice(np.concatenate(parts), device), _HostDevice(entries, device)
+    return t
+
+
+def _robotic_fit_args(features, tabs, order, params, who):
+    if not isinstance(tabs, RoboticFitTables):
+        raise ValueError("%s: tabs must be a RoboticFitTables (ops.robotic_fit_tables)" % who)
+    features = _check(features, "features")
+    if features.dim() != 2:
+        raise ValueError("%s: features must be [N, D], got %s" % (who, tuple(features.shape)))
+    n, d = int(features.shape[0]), int(features.shape[1])
+    n_par = int(params.numel())
+    if n_par % (d + 1):
+        raise ValueError("%s: %d parameters are no Linear(%d, S) with its bias" % (who, n_par, d))
+    s = n_par // (d + 1)
+    if not robotic_supported(d, s, tabs.batch):
+        raise ValueError("%s: %d features, state_dim %d and minibatches of %d are outside srlz_robotic_supported" % (who, d, s, tabs.batch))
+    if not isinstance(order, _HostDevice):
+        order = _HostDevice(np.asarray(order).reshape(-1), features.device)
+    for t in (tabs.idx, tabs.tables, tabs.dir, order):
+        if t.device.device != features.device:
+            raise ValueError("%s: the tables live on %s, the features on %s" % (who, t.device.device, features.device))
+    return features, n, d, s, order
+
+
+def _robotic_buffer(t, name, dtype, numel, device, who, exact=False):
+    if not (torch.is_tensor(t) and t.dtype == dtype and t.device == device and t.is_contiguous()
+            and (t.numel() == numel if exact else t.numel() >= numel)):
+        raise ValueError("%s: %s must be a contiguous %s device tensor of %s%d elements on %s"
+                         % (who, name, dtype, "" if exact else "at least ", numel, device))
+
+
+def robotic_order(ids, device):
+    """A list of minibatch ids (an epoch's order, or the validation minibatches), uploaded without blocking."""
+    return _HostDevice(np.asarray(ids).reshape(-1), device)
+
+
+def robotic_fit(features, tabs, order, params, m, v, t0, lr, running, step_terms=None, last_grad=None, betas=(0.9, 0.999), eps=1e-8):
+    """len(order) consecutive Adam steps of the linear state map under the four robotic priors in ONE launch of srlz_robotic_fit:
+    step s trains on minibatch order[s] of tabs.  No autograd: the kernel owns the backward.  features fp32 [N, D] on the device;
+    params / m / v: float32 [S * D + S] in state_dict order, updated in place; t0: the Adam steps already taken; running float64
+    [4] is added to (the four terms of every step); step_terms: float64 [>= 4 * steps] or None; last_grad: float32 [n_params] or
+    None."""
+    features, n, d, s, order = _robotic_fit_args(features, tabs, order, params, "robotic_fit")
+    dev, n_par, steps = features.device, int(params.numel()), int(order.host.numel())
+    for t, name in ((params, "params"), (m, "m"), (v, "v")):
+        _robotic_buffer(t, name, torch.float32, n_par, dev, "robotic_fit", exact=True)
+    _robotic_buffer(running, "running", torch.float64, 4, dev, "robotic_fit", exact=True)
+    if step_terms is not None:
+        _robotic_buffer(step_terms, "step_terms", torch.float64, 4 * steps, dev, "robotic_fit")
+    if last_grad is not None:
+        _robotic_buffer(last_grad, "last_grad", torch.float32, n_par, dev, "robotic_fit", exact=True)
+    C.robotic_fit(ptr(features), n, d, s, ptr(tabs.idx.device), tabs.idx.host_ptr(), tabs.n, tabs.batch, ptr(tabs.tables.device),
+                  int(tabs.tables.host.numel()), ptr(tabs.dir.device), tabs.dir.host_ptr(), ptr(order.device), order.host_ptr(), steps,
+                  ptr(params), ptr(m), ptr(v), int(t0), float(lr), float(betas[0]), float(betas[1]), float(eps), ptr(running),
+                  ptr(step_terms), ptr(last_grad), stream())
+
+
+_ROBOTIC_TICKET = {}
+
+
+def robotic_eval(features, tabs, order, params, running, workspace=None):
+    """The four terms of the listed minibatches in ONE launch of srlz_robotic_eval, added to running float64 [4] in list order;
+    params are only read.  workspace: a contiguous uint8 device tensor of at least srlz_robotic_eval_workspace(len(order)) bytes,
+    made here when None."""
+    features, n, d, s, order = _robotic_fit_args(features, tabs, order, params, "robotic_eval")
+    dev, count = features.device, int(order.host.numel())
+    _robotic_buffer(params, "params", torch.float32, int(params.numel()), dev, "robotic_eval", exact=True)
+    _robotic_buffer(running, "running", torch.float64, 4, dev, "robotic_eval", exact=True)
+    ticket = _ROBOTIC_TICKET.get(dev.index)
+    if ticket is None:
+        ticket = _ROBOTIC_TICKET[dev.index] = torch.zeros(1, dtype=torch.int32, device=dev)
+    nbytes = int(C.robotic_eval_workspace(count))
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    else:
+        _robotic_buffer(workspace, "workspace", torch.uint8, nbytes, dev, "robotic_eval")
+    C.robotic_eval(ptr(features), n, d, s, ptr(tabs.idx.device), tabs.idx.host_ptr(), tabs.n, tabs.batch, ptr(tabs.tables.device),
+                   int(tabs.tables.host.numel()), ptr(tabs.dir.device), tabs.dir.host_ptr(), ptr(order.device), order.host_ptr(), count,
+                   ptr(params), ptr(running), ptr(workspace), workspace.numel(), ptr(ticket), stream())
